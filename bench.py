@@ -16,7 +16,13 @@ N > 1   rank r owns chunks [r*K, (r+1)*K) of ONE global stream.  Ranks exchange 
         the ranks, so every N shares the N = 1 workload; --scaling weak: 4 GiB per rank (seed
         0xC4 + rank).  The step also gathers the global stream onto rank 0 (RCCL point-to-point into
         its byte offsets, shared bytes ORed on device).
-Run: python bench.py [--gpus N --steps K --warmup W].  With --gpus N > 1 and no WORLD_SIZE in the
+Run: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR].  A plain run sets
+up, warms up, times the K steps and prints the result line (cpu_baseline and bit_exact are null);
+--full adds the round-trip comparison after the warmup, the whole-stream oracle check and the CPU
+baseline described below (--no-verify / --no-cpu leave one of them out again).  --dump-outputs DIR
+writes what the last timed step computed (the compressed stream and the decompressed bytes, as a
+fixed seeded sample plus exact per-64-KiB byte sums, see dump_outputs) as DIR/<name>.npy; the corpus
+is seeded, so two builds run with the same arguments can be compared output for output.  With --gpus N > 1 and no WORLD_SIZE in the
 environment, bench.py starts N ranks itself (torch.distributed.run on 127.0.0.1, before anything
 touches the GPU) and exits with their status; under torch.distributed.run it is one rank.
 N > 1 gathers the global stream onto rank 0 in every step by default (north_star: "RCCL gather over
@@ -51,8 +57,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--size", type=int, default=4 << 30, help="corpus bytes (in total; per rank with --scaling weak)")
     ap.add_argument("--cpu-sample", type=int, default=1 << 30, help="bytes for the CPU baseline leg (about 20 s of oracle work)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-verify", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the round-trip comparison after the "
+                         "warmup, the whole-stream oracle check (bit_exact) and the CPU baseline")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: leave out the oracle check and the CPU baseline")
+    ap.add_argument("--no-verify", action="store_true", help="--full: leave out the round-trip comparison")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy")
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL over xGMI); gloo only to rehearse N>1 on one GPU")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="strong",
                     help="strong (default): --size bytes in total (config 4); weak: --size bytes per rank")
@@ -63,6 +74,9 @@ def main():
     ap.add_argument("--verify-threads", type=int, default=0, help="host threads of the full-stream oracle check "
                     "(0: min(16, cpus / ranks))")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run sets up, warms up, times the steps and prints the line
+        args.no_cpu = args.no_verify = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
@@ -139,6 +153,7 @@ def main():
             r, olen, bits = ctx.inflate_raw(comp.data_ptr(), cbytes, dec.data_ptr(), dec.numel(),
                                             DEV | ndfl.IN_PADDED)
             ndfl.check(r, "inflate")
+            state["inflate_bits"] = bits
         else:
             # one global stream: history halo + seam index + realignment, then range decode with the
             # window chain (ndfl/parallel.py)
@@ -167,7 +182,7 @@ def main():
     for _ in range(args.warmup):
         step()
     progress(rank, f"{args.warmup} warmup steps done")
-    if not args.no_verify:
+    if not args.no_verify and args.warmup > 0:
         assert state["olen"] == n, (state["olen"], n)
         dl = state["dict_len"]
         assert torch.equal(dec[dl:dl + n], data), "round trip mismatch"
@@ -185,6 +200,13 @@ def main():
     t1 = time.perf_counter()
     per = (t1 - t0) / args.steps
     progress(rank, f"{args.steps} timed steps: {per * 1e3:.3f} ms per step")
+    if args.dump_outputs:
+        dl = state["dict_len"]
+        dump_outputs(args.dump_outputs, "" if world == 1 else f".rank{rank}",
+                     {"compressed": comp[:state["cbytes"]], "decompressed": dec[dl:dl + state["olen"]]},
+                     {"compressed_bits": state["endbits"], "decompressed_bytes": state["olen"],
+                      "inflate_consumed_bits": state.get("inflate_bits", -1)})
+        progress(rank, f"outputs written to {args.dump_outputs}")
     c_total = state["cbytes"]
     if dist is not None:
         cdev = "cpu" if args.backend == "gloo" else "cuda"
@@ -256,6 +278,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(per * 1e3, 3),
             "higher_is_better": True,
             "scaling": args.scaling,
@@ -298,6 +321,45 @@ _T_START = time.perf_counter()
 def progress(rank, msg):
     """One progress line on stderr (the JSON result stays the only stdout line)."""
     print(f"[bench rank {rank} +{time.perf_counter() - _T_START:.1f}s] {msg}", file=sys.stderr, flush=True)
+
+
+DUMP_HEAD = 1 << 20        # leading bytes of an output written as they are
+DUMP_SAMPLE = 3 << 20      # seeded positions over the whole output written after them
+DUMP_BLOCK = 65536         # every byte of an output enters one sum per DUMP_BLOCK bytes
+
+
+def dump_outputs(dirpath, suffix, arrays, sizes):
+    """Write the last timed step's outputs (device uint8 tensors) so that two builds can be compared
+    output for output.  Per output <name>: <name>.npy (float32) holds the whole output if it has at
+    most DUMP_HEAD + DUMP_SAMPLE bytes, otherwise its first DUMP_HEAD bytes followed by the bytes at
+    DUMP_SAMPLE positions drawn once with a seeded host generator (sorted, fixed per output length);
+    <name>_block_sums.npy (float64, exact) holds the byte sum of every DUMP_BLOCK bytes, so every byte
+    of the output is covered.  sizes.npy (float64) holds the lengths the calls returned, in the order
+    of sizes_names.txt.  About 33 MB for the default workload."""
+    import numpy as np
+    import torch
+    os.makedirs(dirpath, exist_ok=True)
+    for k, (name, x) in enumerate(arrays.items()):
+        m = x.numel()
+        if m <= DUMP_HEAD + DUMP_SAMPLE:
+            picked = x
+        else:
+            g = torch.Generator().manual_seed(0xD0 + k)
+            pos = torch.randint(DUMP_HEAD, m, (DUMP_SAMPLE,), generator=g).sort().values
+            picked = torch.cat([x[:DUMP_HEAD], x[pos.to(x.device)]])
+        np.save(os.path.join(dirpath, f"{name}{suffix}.npy"), picked.cpu().numpy().astype(np.float32))
+        sums = []
+        batch = 4096 * DUMP_BLOCK                       # 256 MiB at a time bounds the temporaries
+        for b0 in range(0, m - m % DUMP_BLOCK, batch):
+            b1 = min(m - m % DUMP_BLOCK, b0 + batch)
+            sums.append(x[b0:b1].view(-1, DUMP_BLOCK).sum(dim=1, dtype=torch.int64))
+        if m % DUMP_BLOCK:
+            sums.append(x[m - m % DUMP_BLOCK:].sum(dtype=torch.int64).reshape(1))
+        s = torch.cat(sums) if sums else torch.zeros(0, dtype=torch.int64)
+        np.save(os.path.join(dirpath, f"{name}_block_sums{suffix}.npy"), s.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(dirpath, f"sizes{suffix}.npy"), np.array(list(sizes.values()), dtype=np.float64))
+    with open(os.path.join(dirpath, f"sizes_names{suffix}.txt"), "w") as f:
+        f.write("\n".join(sizes) + "\n")
 
 
 def launch_ranks(n):
