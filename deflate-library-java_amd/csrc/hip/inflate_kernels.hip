@@ -352,9 +352,6 @@ __device__ __forceinline__ bool strict_stored(const In& in, uint64_t p) {
 #ifndef NDFL_FIND_WPE
 #define NDFL_FIND_WPE 3
 #endif
-#ifndef NDFL_FIND_LASTBLK
-#define NDFL_FIND_LASTBLK 0
-#endif
 #ifndef NDFL_STRICT_WPE
 #define NDFL_STRICT_WPE 5
 #endif
@@ -394,11 +391,7 @@ __device__ __forceinline__ void find_word_wave(const In& in, uint64_t t, uint64_
     uint32_t valid = 0xFFFFFFFFu;
     if (p0 + 35 > nbits) valid = (nbits >= p0 + 3) ? (uint32_t)((1ull << (nbits - p0 - 2)) - 1) : 0u;
     if (p0 + 32 > scan_end) valid &= p0 < scan_end ? (uint32_t)((1ull << (scan_end - p0)) - 1) : 0u;
-#if NDFL_FIND_LASTBLK
-    const uint32_t notfinal = ~0u;
-#else
     const uint32_t notfinal = ~w0;
-#endif
     const uint32_t h4 = (uint32_t)(W >> 4), h5 = (uint32_t)(W >> 5), h6 = (uint32_t)(W >> 6),
                    h7 = (uint32_t)(W >> 7), d9 = (uint32_t)(W >> 9), d10 = (uint32_t)(W >> 10),
                    d11 = (uint32_t)(W >> 11), d12 = (uint32_t)(W >> 12);
@@ -904,7 +897,7 @@ ndfl_inflate_alias_mark_kernel(const uint64_t* cands, uint64_t* info, const uint
 constexpr uint32_t OB_NB = 24;
 constexpr uint32_t OB_WORDS = 2 * OB_NB;      // tot, cursor
 constexpr size_t CTK_BYTES = 512;             // chain ticket, nord, two bucket orders, first error
-static_assert((16 + 2 * OB_WORDS + 1) * 4 <= CTK_BYTES, "ticket buffer layout");
+
 template <class Bk>
 __device__ __forceinline__ void border_count(Bk bk, uint32_t n, uint32_t* ob) {
     __shared__ uint32_t h[OB_NB];
@@ -1109,33 +1102,9 @@ ndfl_inflate_summary_kernel(const ChainRes* er, const EmitChain* chains, uint64_
     }
 }
 
-// Count-pass records of every round of a chain: each lane's exact segment, so the emit pass
-// decodes each segment once instead of re-running the speculation.  Records come from a pool and
-// are linked per chain in decode order (chain slot -> head record -> next ...).
-constexpr uint32_t NOREC = 0xFFFFFFFFu;
-struct SegMeta {
-    uint32_t ft, kind_ft, reason_ft, next;
-    uint64_t end_ft, exit63;
-    uint32_t pw, pad;     // the round's words per lane segment (staging geometry)
-    uint64_t rs;          // staging origin: the record's lane 0 segment start (absolute bit)
-};
-struct SegPool {
-    uint64_t* start;      // [nrec][64]
-    uint32_t* cnt;        // [nrec][64]
-    SegMeta* meta;        // [nrec]
-    uint32_t* head;       // [nslot] first record of the chain counted at that slot (NOREC: none)
-    uint32_t* ctr;        // records handed out
-    uint32_t nrec;
-    uint64_t nslot;
-    // per Huffman block: the count pass's decode tables and header fields (BT_BYTES each), so the
-    // emit pass loads them instead of parsing the header and building the tables again; a block's
-    // first round record names its table record in SegMeta::pad (NOREC: none)
-    char* bt;
-    uint32_t* bctr;       // table records handed out
-    uint32_t nbt;
-};
-constexpr uint32_t BT_BYTES = 6720;   // wv::Tabs (6656) + hdr bit, data bit (u64 each), bfinal, btype, ed, pad
-
+// Count-pass records (round records, table records) and the words the host shares with the kernels
+#include "inflate_records.hpp"
+static_assert((CT_ORDER + 2 * OB_WORDS + 1) * 4 <= CTK_BYTES, "ticket buffer layout");
 #include "inflate_wave.hpp"
 #include "inflate_wg.hpp"
 
@@ -1321,6 +1290,26 @@ static int resolve_rounds(InflateScratch& S, hipStream_t s, uint8_t* d_out, uint
     }
 }
 
+// NDFL_STATS: the strict stage's counters and the count pass's wave clocks, from d_stats (both decode
+// paths print them)
+static int print_count_stats(InflateScratch& S, bool phase_clock_note) {
+    uint32_t st[64] = {0};
+    INF_CHK(hipMemcpy(st, S.d_stats, 256, hipMemcpyDeviceToHost));
+    const unsigned long long* ss = (const unsigned long long*)(st + SW_STRICT64);
+    fprintf(stderr, "[ndfl] strict stage: %llu waves, %llu loop trips (%llu refills), %llu lane-symbol steps\n",
+            ss[3], ss[0], ss[1], ss[2]);
+    const uint64_t* t64 = (const uint64_t*)(st + SW_CLOCK64);
+    fprintf(stderr, "[ndfl] count wave-time (ms x waves, 100 MHz clock%s): header %.1f spec %.1f "
+            "verify %.1f phases %.1f serial %.1f record %.1f build %.1f phase-mapped %.1f\n",
+            phase_clock_note ? "; -DNDFL_PHASE_CLOCK builds" : "", t64[0] * 1e-5,
+            t64[1] * 1e-5, t64[2] * 1e-5, t64[3] * 1e-5, t64[4] * 1e-5, t64[5] * 1e-5, t64[6] * 1e-5, t64[7] * 1e-5);
+    const double span = (double)(t64[9] - ~t64[10]);
+    fprintf(stderr, "[ndfl] count waves %llu: busy %.1f ms x waves, span %.3f ms, occupancy %.3f, longest chain %.3f ms\n",
+            (unsigned long long)t64[11], t64[8] * 1e-5, span * 1e-5, t64[11] ? t64[8] / (span * t64[11]) : 0.0,
+            t64[12] * 1e-5);
+    return 0;
+}
+
 // Segment-record pool for `nstarts` chain starts (SegPool): the rounds of all chains, one head per
 // counted chain start, with room for repairs, and the per-block table records.
 static int setup_pool(InflateScratch& S, hipStream_t s, uint64_t nstarts, uint64_t nbits) {
@@ -1336,10 +1325,10 @@ static int setup_pool(InflateScratch& S, hipStream_t s, uint64_t nstarts, uint64
     pool.cnt = (uint32_t*)(pool.start + nrec * 64);
     pool.meta = (SegMeta*)(pool.cnt + nrec * 64);
     pool.head = (uint32_t*)(pool.meta + nrec);
-    pool.ctr = (uint32_t*)S.d_stats + 12;
-    pool.bctr = (uint32_t*)S.d_stats + 13;
+    pool.ctr = (uint32_t*)S.d_stats + SW_REC_CTR;
+    pool.bctr = (uint32_t*)S.d_stats + SW_TREC_CTR;
     pool.nbt = (uint32_t)nbt;
-    pool.bt = (char*)(((uintptr_t)(pool.head + nslot) + 63) & ~(uintptr_t)63);
+    pool.bt = (TabRec*)(((uintptr_t)(pool.head + nslot) + 63) & ~(uintptr_t)63);
     pool.nrec = (uint32_t)nrec;
     pool.nslot = nslot;
     S.pool = pool;
@@ -1435,7 +1424,7 @@ static int inflate_devlink(InflateScratch& S, hipStream_t s, const uint32_t* d_w
     }
     INF_CHK(hipMemcpyAsync((void*)hinfo, info, (LI_NREP + 1) * 8, hipMemcpyDeviceToHost, s));
     hinfo[LI_QCOUNT] = 0;
-    INF_CHK(hipMemcpyAsync((void*)(hinfo + LI_QCOUNT), (const uint32_t*)S.d_stats + 8, 4, hipMemcpyDeviceToHost, s));
+    INF_CHK(hipMemcpyAsync((void*)(hinfo + LI_QCOUNT), (const uint32_t*)S.d_stats + SW_QCOUNT, 4, hipMemcpyDeviceToHost, s));
     INF_CHK(hipStreamSynchronize(s));                          // (1) the number of chain starts
     if ((uint32_t)hinfo[LI_QCOUNT] > S.q_cap && !S.q_full) { S.q_min = (uint32_t)hinfo[LI_QCOUNT] + 65536; return FIND_OVERFLOW; }
     const uint64_t n = hinfo[LI_NCAND];
@@ -1460,9 +1449,9 @@ static int inflate_devlink(InflateScratch& S, hipStream_t s, const uint32_t* d_w
     uint32_t* d_order = (uint32_t*)((char*)S.d_stops + n * 8);
     if (!S.d_cticket) INF_CHK(hipMalloc(&S.d_cticket, CTK_BYTES));
     INF_CHK(hipMemsetAsync(S.d_cticket, 0, CTK_BYTES, s));
-    uint32_t* d_nord = (uint32_t*)S.d_cticket + 8;
-    uint32_t* d_nflat = (uint32_t*)S.d_cticket + 4;
-    uint32_t* d_ob = (uint32_t*)S.d_cticket + 16;                      // count order: tot, cursor
+    uint32_t* d_nord = (uint32_t*)S.d_cticket + CT_NORD;
+    uint32_t* d_nflat = (uint32_t*)S.d_cticket + CT_NFLAT;
+    uint32_t* d_ob = (uint32_t*)S.d_cticket + CT_ORDER;                    // count order: tot, cursor
     const uint32_t otiles = (ncand + SCAN_TILE - 1) / SCAN_TILE;
     if (!S.d_ph) INF_CHK(hipMalloc(&S.d_ph, (size_t)std::max(COUNT_WAVES, EMIT_WAVES) * sizeof(wv::PhArr)));
     const bool stats_on = S.knobs.stats;
@@ -1519,13 +1508,15 @@ static int inflate_devlink(InflateScratch& S, hipStream_t s, const uint32_t* d_w
             cnt[st]++; tsum[st] += t; tmax[st] = std::max<uint64_t>(tmax[st], t); blk[st] += cr[k].pad & 0xFFFFu;
         }
         if (flat_on) {
-            uint32_t fw[12] = {0};
-            INF_CHK(hipMemcpy(fw, (uint32_t*)S.d_cticket + 4, 48, hipMemcpyDeviceToHost));
+            uint32_t fw[CT_ORDER] = {0};
+            INF_CHK(hipMemcpy(fw, S.d_cticket, sizeof(fw), hipMemcpyDeviceToHost));
+            const uint32_t* why = fw + CT_FLAT_WHY;
             fprintf(stderr, "[ndfl] count flat groups sent back: (unused) %u, full-table tokens %u, "
-                    "error %u, chain goes on %u, table %u\n", fw[7], fw[8], fw[9], fw[10], fw[11]);
-            const unsigned long long gt = (unsigned long long)fw[2] | ((unsigned long long)fw[3] << 32);
+                    "error %u, chain goes on %u, table %u\n", why[1], why[2], why[3], why[4], why[5]);
+            const uint32_t nfl = fw[CT_NFLAT];
+            const unsigned long long gt = (unsigned long long)fw[CT_FLAT_TIME64] | ((unsigned long long)fw[CT_FLAT_TIME64 + 1] << 32);
             fprintf(stderr, "[ndfl] count flat groups: %u chains in %u groups, %u sent back to the wave decode, "
-                    "group wave time %.3f ms mean\n", fw[0], (fw[0] + 63) / 64, fw[1], fw[0] ? gt * 1e-5 / ((fw[0] + 63) / 64) : 0.0);
+                    "group wave time %.3f ms mean\n", nfl, (nfl + 63) / 64, fw[CT_FLAT_REDO], nfl ? gt * 1e-5 / ((nfl + 63) / 64) : 0.0);
 #ifdef NDFL_FLAT_PROF
             unsigned long long fpv[4] = {0, 0, 0, 0}, z[4] = {0, 0, 0, 0};
             INF_CHK(hipMemcpyFromSymbol(fpv, HIP_SYMBOL(wv::g_flat_prof), 32));
@@ -1597,7 +1588,7 @@ static int inflate_devlink(InflateScratch& S, hipStream_t s, const uint32_t* d_w
     INF_CHK(hipGetLastError());
     // the emit pass claims the linked chains costliest first (the count pass's order buffer is free)
     {
-        uint32_t* d_eob = (uint32_t*)S.d_cticket + 16 + OB_WORDS;      // emit order: tot, cursor (zeroed above)
+        uint32_t* d_eob = (uint32_t*)S.d_cticket + CT_ORDER + OB_WORDS;     // emit order: tot, cursor (zeroed above)
         const uint32_t etiles = (ncand + SCAN_TILE - 1) / SCAN_TILE;    // (chains <= candidates)
         hipLaunchKernelGGL(ndfl_inflate_emit_order_count_kernel, dim3(etiles), dim3(SCAN_T), 0, s,
                            (const EmitChain*)S.d_chains, (const uint64_t*)info, d_eob);
@@ -1670,7 +1661,7 @@ static int inflate_devlink(InflateScratch& S, hipStream_t s, const uint32_t* d_w
     }
     INF_CHK(hipEventRecord(S.ev[5], s));
     {
-        uint32_t* d_first = (uint32_t*)S.d_cticket + 16 + 2 * OB_WORDS;
+        uint32_t* d_first = (uint32_t*)S.d_cticket + CT_ORDER + 2 * OB_WORDS;
         INF_CHK(hipMemsetAsync(d_first, 0xFF, 4, s));
         hipLaunchKernelGGL(ndfl_inflate_first_error_kernel, dim3((ncand + SCAN_TILE - 1) / SCAN_TILE), dim3(SCAN_T), 0, s,
                            (const ChainRes*)S.d_res, (const uint64_t*)info, d_first);
@@ -1689,23 +1680,14 @@ static int inflate_devlink(InflateScratch& S, hipStream_t s, const uint32_t* d_w
     INF_CHK(hipMemcpyAsync((void*)hinfo, info, LI_WORDS * 8, hipMemcpyDeviceToHost, s));
     INF_CHK(hipStreamSynchronize(s));                          // (2) the summary
     if (stats_on) {
-        uint32_t st[64] = {0};
-        INF_CHK(hipMemcpy(st, S.d_stats, 256, hipMemcpyDeviceToHost));
-        const uint64_t* t64 = (const uint64_t*)(st + 32);
+        uint32_t st[3] = {0, 0, 0};
+        INF_CHK(hipMemcpy(st, S.d_stats, sizeof(st), hipMemcpyDeviceToHost));
         fprintf(stderr, "[ndfl] device link: chains %llu of %u candidates; count pass: slow-verify lanes %u fixups %u "
-                "rounds %u\n", (unsigned long long)hinfo[LI_NCH], ncand, st[0], st[1], st[2]);
-        const unsigned long long* ss = (const unsigned long long*)(st + 16);
-        fprintf(stderr, "[ndfl] strict stage: %llu waves, %llu loop trips (%llu refills), %llu lane-symbol steps\n",
-                ss[3], ss[0], ss[1], ss[2]);
+                "rounds %u\n", (unsigned long long)hinfo[LI_NCH], ncand, st[SW_NSLOW], st[SW_NFIX], st[SW_NROUND]);
         fprintf(stderr, "[ndfl] emit: %u pending 32-byte groups before the resolve rounds, %u after six\n",
                 (uint32_t)(hinfo[LI_WORDS - 3] & 0xFFFFFFFFu), (uint32_t)(hinfo[LI_WORDS - 1] & 0xFFFFFFFFu));
-        fprintf(stderr, "[ndfl] count wave-time (ms x waves, 100 MHz clock; -DNDFL_PHASE_CLOCK builds): header %.1f spec %.1f "
-                "verify %.1f phases %.1f serial %.1f record %.1f build %.1f phase-mapped %.1f\n", t64[0] * 1e-5,
-                t64[1] * 1e-5, t64[2] * 1e-5, t64[3] * 1e-5, t64[4] * 1e-5, t64[5] * 1e-5, t64[6] * 1e-5, t64[7] * 1e-5);
-        const double span = (double)(t64[9] - ~t64[10]);
-        fprintf(stderr, "[ndfl] count waves %llu: busy %.1f ms x waves, span %.3f ms, occupancy %.3f, longest chain %.3f ms\n",
-                (unsigned long long)t64[11], t64[8] * 1e-5, span * 1e-5, t64[11] ? t64[8] / (span * t64[11]) : 0.0,
-                t64[12] * 1e-5);
+        rc = print_count_stats(S, true);
+        if (rc) return rc;
     }
     const uint64_t lflags = hinfo[LI_FLAGS];
     if (lflags & LF_REPAIR) return LINK_FALLBACK;
@@ -1794,7 +1776,7 @@ static int find_headers(InflateScratch& S, hipStream_t s, const uint32_t* d_w, u
         INF_CHK(inf_ensure(&S.d_q, &S.d_q_cap, (uint64_t)qcap * 8 + 64));
     }
     S.q_cap = qcap;
-    uint32_t* d_qcount = (uint32_t*)S.d_stats + 8;
+    uint32_t* d_qcount = (uint32_t*)S.d_stats + SW_QCOUNT;
     uint64_t* d_qlist = (uint64_t*)((char*)S.d_q + 64);
     static const uint32_t strict_grid = [] {
         int dev = 0, ncu = 0, per = 0;
@@ -1805,7 +1787,7 @@ static int find_headers(InflateScratch& S, hipStream_t s, const uint32_t* d_w, u
             return 1280u;
         return (uint32_t)(ncu * per);
     }();
-    unsigned long long* sst = S.knobs.stats ? (unsigned long long*)((uint32_t*)S.d_stats + 16) : nullptr;
+    unsigned long long* sst = S.knobs.stats ? (unsigned long long*)((uint32_t*)S.d_stats + SW_STRICT64) : nullptr;
     if (nw32) {
         const uint32_t fgrid = (uint32_t)((nw32 + 256 * FIND_WPT - 1) / (256 * FIND_WPT));
         hipLaunchKernelGGL(ndfl_inflate_find_compact_kernel, dim3(fgrid), dim3(256), 0, s, d_w, nwords, nbits, d_qlist,
@@ -1813,7 +1795,7 @@ static int find_headers(InflateScratch& S, hipStream_t s, const uint32_t* d_w, u
         INF_CHK(hipGetLastError());
         hipLaunchKernelGGL(ndfl_inflate_strict_kernel, dim3(strict_grid), dim3(256), 0, s, d_w, nwords, nbits,
                            (const uint64_t*)d_qlist, (const uint32_t*)d_qcount, qcap, d_cnt, d_list,
-                           (uint32_t*)S.d_stats + 10, sst);
+                           (uint32_t*)S.d_stats + SW_STRICT_TICKET, sst);
         INF_CHK(hipGetLastError());
     }
     return 0;
@@ -1843,7 +1825,7 @@ static int inflate_headers(InflateScratch& S, hipStream_t s, const uint8_t* in, 
         INF_CHK(hipMemsetAsync(S.d_stats, 0, 512, s));
         INF_CHK(hipMemsetAsync(d_cnt, 0, (uint64_t)nseg * 4, s));
         INF_RC(find_headers(S, s, d_w, nwords, nbits, 0, NONE, d_cnt, d_list));
-        INF_CHK(hipMemcpyAsync(&qc, (uint32_t*)S.d_stats + 8, 4, hipMemcpyDeviceToHost, s));
+        INF_CHK(hipMemcpyAsync(&qc, (uint32_t*)S.d_stats + SW_QCOUNT, 4, hipMemcpyDeviceToHost, s));
         INF_CHK(hipStreamSynchronize(s));
         if (qc <= S.q_cap || S.q_full) break;
         S.q_min = qc + 65536;
@@ -1917,7 +1899,7 @@ refind:
     std::vector<uint32_t> hcnt(nseg);
     uint32_t hqc = 0;
     INF_CHK(hipMemcpyAsync(hcnt.data(), d_cnt, nseg * 4ull, hipMemcpyDeviceToHost, s));
-    INF_CHK(hipMemcpyAsync(&hqc, (const uint32_t*)S.d_stats + 8, 4, hipMemcpyDeviceToHost, s));
+    INF_CHK(hipMemcpyAsync(&hqc, (const uint32_t*)S.d_stats + SW_QCOUNT, 4, hipMemcpyDeviceToHost, s));
     INF_CHK(hipStreamSynchronize(s));
     if (hqc > S.q_cap && !S.q_full && finds++ == 0) { S.q_min = hqc + 65536; goto refind; }
     std::vector<uint64_t> hoff(nseg + 1);
@@ -1948,27 +1930,12 @@ refind:
     INF_CHK(inf_ensure(&S.d_cands, &S.d_cands_cap, (ncand + 1) * 8ull));
     INF_CHK(hipMemcpyAsync(S.d_cands, sorted_cand.data(), ncand * 8ull, hipMemcpyHostToDevice, s));
     const uint64_t limit = std::min(end_bit, nbits);
-    // segment records: a pool for the rounds of all chains, one head per counted chain start (index
-    // in `starts`), with room for repairs
-    const uint64_t nslot = starts.size() + std::max<uint64_t>(4096, starts.size() / 2);
-    const uint64_t nrec = std::min<uint64_t>(0xFFFFFFF0ull, 2 * starts.size() + nbits / (wv::MAX_SPAN / 2) + 65536);
-    // table records: at most one per block; bounded (a stream of tiny blocks parses the rest again)
-    const uint64_t nbt = std::min<uint64_t>(nrec, S.knobs.no_bt ? 0 : (1u << 18));
-    const uint64_t seg_bytes = nrec * (64 * 8 + 64 * 4 + sizeof(SegMeta)) + nslot * 4 + 64 + nbt * BT_BYTES;
-    INF_CHK(inf_ensure(&S.d_seg, &S.d_seg_cap, seg_bytes));
-    SegPool pool;
-    pool.start = (uint64_t*)S.d_seg;
-    pool.cnt = (uint32_t*)(pool.start + nrec * 64);
-    pool.meta = (SegMeta*)(pool.cnt + nrec * 64);
-    pool.head = (uint32_t*)(pool.meta + nrec);
-    pool.ctr = (uint32_t*)S.d_stats + 12;
-    pool.bctr = (uint32_t*)S.d_stats + 13;
-    pool.nbt = (uint32_t)nbt;
-    pool.bt = (char*)(((uintptr_t)(pool.head + nslot) + 63) & ~(uintptr_t)63);
-    pool.nrec = (uint32_t)nrec;
-    pool.nslot = nslot;
-    S.pool = pool;
-    INF_CHK(hipMemsetAsync(pool.head, 0xFF, nslot * 4, s));
+    // segment records: one head per counted chain start (index in `starts`)
+    {
+        const int prc = setup_pool(S, s, starts.size(), nbits);
+        if (prc) return prc;
+    }
+    const SegPool pool = S.pool;
 
     const bool stats_on = S.knobs.stats;
     std::vector<ChainRes> res;
@@ -2136,23 +2103,13 @@ refind:
     S.flat_chains = 0;
     S.candidates = sorted_cand.size();
     if (S.knobs.stats) {
-        uint32_t st[64] = {0};
-        INF_CHK(hipMemcpy(st, S.d_stats, 256, hipMemcpyDeviceToHost));
-        st[4] = st[8];
+        uint32_t st[SW_QCOUNT + 1] = {0};
+        INF_CHK(hipMemcpy(st, S.d_stats, sizeof(st), hipMemcpyDeviceToHost));
         fprintf(stderr, "[ndfl] finder quick survivors %u; count pass: chains %zu candidates %zu repairs %llu "
-                "slow-verify lanes %u fixups %u rounds %u\n", st[4], chains.size(), sorted_cand.size(),
-                (unsigned long long)S.repairs, st[0], st[1], st[2]);
-        const uint64_t* t64 = (const uint64_t*)(st + 32);
-        const unsigned long long* ss = (const unsigned long long*)(st + 16);
-        fprintf(stderr, "[ndfl] strict stage: %llu waves, %llu loop trips (%llu refills), %llu lane-symbol steps\n",
-                ss[3], ss[0], ss[1], ss[2]);
-        fprintf(stderr, "[ndfl] count wave-time (ms x waves, 100 MHz clock): header %.1f spec %.1f verify %.1f phases %.1f "
-                "serial %.1f record %.1f build %.1f phase-mapped %.1f\n", t64[0] * 1e-5, t64[1] * 1e-5, t64[2] * 1e-5, t64[3] * 1e-5,
-                t64[4] * 1e-5, t64[5] * 1e-5, t64[6] * 1e-5, t64[7] * 1e-5);
-        const double span = (double)(t64[9] - ~t64[10]);
-        fprintf(stderr, "[ndfl] count waves %llu: busy %.1f ms x waves, span %.3f ms, occupancy %.3f, longest chain %.3f ms\n",
-                (unsigned long long)t64[11], t64[8] * 1e-5, span * 1e-5, t64[11] ? t64[8] / (span * t64[11]) : 0.0,
-                t64[12] * 1e-5);
+                "slow-verify lanes %u fixups %u rounds %u\n", st[SW_QCOUNT], chains.size(), sorted_cand.size(),
+                (unsigned long long)S.repairs, st[SW_NSLOW], st[SW_NFIX], st[SW_NROUND]);
+        const int prc = print_count_stats(S, false);
+        if (prc) return prc;
     }
     const uint64_t total = off - dict_len;
     ht[3] = hnow();
@@ -2200,7 +2157,7 @@ refind:
     S.last_ms_emit = ms;
     if (stats_on) {
         uint64_t t64[48];
-        INF_CHK(hipMemcpy(t64, (const char*)S.d_stats + 128, sizeof(t64), hipMemcpyDeviceToHost));
+        INF_CHK(hipMemcpy(t64, (const uint32_t*)S.d_stats + SW_CLOCK64, sizeof(t64), hipMemcpyDeviceToHost));
         const double span = (double)(t64[17] - ~t64[18]);
         fprintf(stderr, "[ndfl] emit waves %llu: busy %.1f ms x waves, span %.3f ms, occupancy %.3f, longest chain %.3f ms\n",
                 (unsigned long long)t64[19], t64[16] * 1e-5, span * 1e-5, t64[19] ? t64[16] / (span * t64[19]) : 0.0,
@@ -2301,7 +2258,7 @@ static int inflate_tail_map(InflateScratch& S, hipStream_t s, uint64_t n, uint32
     if (n > S.p_nbytes) return -1;
     if (n == 0) return 0;
     if (!S.h_cnt) INF_CHK(hipHostMalloc(&S.h_cnt, 64, 0));
-    uint32_t* d_fail = (uint32_t*)S.d_stats + 14;
+    uint32_t* d_fail = (uint32_t*)S.d_stats + SW_TAIL_FAIL;
     INF_CHK(hipMemsetAsync(d_fail, 0, 4, s));
     hipLaunchKernelGGL(ndfl_inflate_tail_map_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s,
                        (const uint32_t*)S.d_pend, (const uint32_t*)S.d_ref, (const uint8_t*)S.p_out, S.p_nbytes - n, n,
@@ -2318,7 +2275,7 @@ static int inflate_tail(InflateScratch& S, hipStream_t s, uint64_t n, uint8_t* d
     if (n > S.p_nbytes) return -1;
     if (n == 0) return 0;
     if (!S.h_cnt) INF_CHK(hipHostMalloc(&S.h_cnt, 64, 0));
-    uint32_t* d_fail = (uint32_t*)S.d_stats + 14;
+    uint32_t* d_fail = (uint32_t*)S.d_stats + SW_TAIL_FAIL;
     INF_CHK(hipMemsetAsync(d_fail, 0, 4, s));
     hipLaunchKernelGGL(ndfl_inflate_tail_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s,
                        (const uint32_t*)S.d_pend, (const uint32_t*)S.d_ref, (const uint8_t*)S.p_out, S.p_nbytes - n, n,

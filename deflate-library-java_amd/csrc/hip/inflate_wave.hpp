@@ -25,37 +25,9 @@
 namespace wv {
 using namespace inf;
 
-constexpr uint32_t LB = 10;                 // literal/length primary bits
-constexpr uint32_t DB = 8;                  // distance primary bits
 // table entry: [4:0] code length (0: longer than the primary), [8:5] extra bits, [10:9] kind,
-// [31:16] literal byte / run base / distance base
+// [31:16] literal byte / run base / distance base (Tabs, TabsG: inflate_records.hpp)
 enum : uint32_t { K_LIT = 0, K_LEN = 1, K_EOB = 2, K_BAD = 3 };
-enum : uint32_t { T_EXIT = 0, T_EOB = 1, T_ERR = 2 };
-
-// Codes longer than the primary: a second-level table per primary prefix when they fit in the
-// extension area (the primary entry then points at it: length 0, [8:5] index bits, [31:16] offset),
-// otherwise the canonical slow path, whose arrays take the extension area instead (primary entry 0).
-constexpr uint32_t LX = 320;                // literal/length extension words
-constexpr uint32_t DX = 64;                 // distance extension words
-struct Tabs {
-    uint32_t lit[1u << LB];
-    uint32_t dst[1u << DB];
-    // sub-tables, or (fallback) the entry of every symbol in canonical order [0, n), the
-    // left-justified 15-bit upper limit of each length [n, n + 16), first code and rank offset per
-    // length (u16) [n + 16, n + 32)
-    uint32_t lx[LX];
-    uint32_t dx[DX];
-};
-
-// The same tables split over two memories (the fast emit pass): the primary tables in LDS, the
-// extension areas -- read only for codes longer than the primary -- in the count pass's table
-// record in global memory.
-struct TabsG {
-    const uint32_t* lit;
-    const uint32_t* dst;
-    const uint32_t* lx;
-    const uint32_t* dx;
-};
 
 struct Shared {
     Tabs t;
@@ -151,13 +123,7 @@ struct Tok {
 constexpr uint32_t LPW = NDFL_LPW;             // words per lane segment at most (448 bits by default)
 constexpr uint32_t SW = LPW + 4;               // staged words per lane region (+ the tail window)
 constexpr uint64_t RSPAN = 64ull * LPW * 32;   // round span cap (bits)
-// Words per lane segment at least: a short round (a small block, a block's last round) is split
-// over fewer lanes rather than into segments too short for a speculative decode to meet its true
-// token boundaries before the segment ends (every such lane otherwise costs a fix-up decode).
-#ifndef NDFL_PW_MIN
-#define NDFL_PW_MIN 4
-#endif
-static_assert(NDFL_PW_MIN >= 1 && NDFL_PW_MIN <= NDFL_LPW, "NDFL_PW_MIN");
+static_assert(seg_pw(1) >= 1 && seg_pw(1) <= LPW, "NDFL_PW_MIN");      // (the shortest segment)
 
 struct Stage {
     uint32_t w[SW * 64];
@@ -175,26 +141,22 @@ __device__ __forceinline__ Geo make_geo(const In& in, uint64_t rs, uint64_t E, u
     g.r0 = (uint32_t)(rs - g.base);
     g.re = (uint32_t)(E - g.base);
     const uint32_t span = g.re - g.r0;
-    g.pw = pw ? pw : max((uint32_t)NDFL_PW_MIN, ((span + 63) / 64 + 31) / 32);
+    g.pw = pw ? pw : seg_pw(span);
     g.nb = (uint32_t)min(in.nbits - min(in.nbits, g.base), (uint64_t)0xFFFFFFFFu);
     return g;
 }
 // lane j's segment [s, e) (relative bits); lane 63 ends at the round end
 __device__ __forceinline__ void lane_seg(const Geo& g, int lane, uint32_t& s, uint32_t& e) {
     const uint32_t per = g.pw * 32;
-    s = min(g.r0 + (uint32_t)lane * per, g.re);
-    e = lane == 63 ? g.re : min(g.r0 + (uint32_t)(lane + 1) * per, g.re);
+    s = seg_start(g.r0, per, g.re, (uint32_t)lane);
+    e = seg_end(g.r0, per, g.re, (uint32_t)lane);
 }
 
 // Stage the round's input (all lanes call).  Words past the input end read the zero padding.
-// NDFL_STAGE_CPOL: cache policy of the staging loads (2 = non-temporal: the input is read once and
-// should not push the emit pass's partly written output lines out of L2; measured: 2 is ~1 ms
-// slower and leaves the emit write traffic unchanged, 20.0 vs 21.5 GB).  Touching the next round's
+// The staging loads use the default cache policy (measured: non-temporal loads, policy 2, are ~1 ms
+// slower and leave the emit write traffic unchanged, 20.0 vs 21.5 GB).  Touching the next round's
 // input into L2 after each staging (one LDS-DMA dword per 128-byte line, round 5) made count and
 // emit slower too (+0.3 / +0.4 ms, profiles/r05_ab_stage_touch.txt).
-#ifndef NDFL_STAGE_CPOL
-#define NDFL_STAGE_CPOL 0
-#endif
 __device__ __forceinline__ void stage_round(const In& in, const Geo& g, Stage& st, int lane) {
     const uint64_t w0 = (g.base >> 5) + (uint64_t)lane * g.pw;
     const uint64_t wmax = in.nwords + 60;          // inside the IN_PAD zero bytes after the input
@@ -202,7 +164,7 @@ __device__ __forceinline__ void stage_round(const In& in, const Geo& g, Stage& s
 #pragma unroll 4
     for (uint32_t i = 0; i < SW; i++)
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(in.w + min(w0 + i, wmax)),
-                                         (__attribute__((address_space(3))) void*)&st.w[i * 64], 4, 0, NDFL_STAGE_CPOL);
+                                         (__attribute__((address_space(3))) void*)&st.w[i * 64], 4, 0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 }
@@ -216,20 +178,6 @@ struct Lv {
     __device__ __forceinline__ void win(uint32_t pos, uint32_t& lo, uint32_t& hi) const {
         const uint32_t* q = p + ((pos >> 5) - rw) * 64;
         const uint32_t a = q[0], b = q[64], c = q[128];
-        lo = __builtin_amdgcn_alignbit(b, a, pos & 31);
-        hi = __builtin_amdgcn_alignbit(c, b, pos & 31);
-    }
-};
-// The lane's view of a round read straight from the input in global memory (the fast emit pass):
-// the same region-relative words as Lv, through L1/L2 instead of an LDS stage.  Reads up to the
-// region's end plus the tail words, inside the IN_PAD zero bytes after the input (as the stage).
-struct Gv {
-    const uint32_t* q;     // the lane's region word 0 in the input
-    uint32_t rw;           // region's first word (relative to base)
-    __device__ __forceinline__ uint32_t ld(uint32_t i) const { return q[i]; }
-    __device__ __forceinline__ void win(uint32_t pos, uint32_t& lo, uint32_t& hi) const {
-        const uint32_t i = (pos >> 5) - rw;
-        const uint32_t a = q[i], b = q[i + 1], c = q[i + 2];
         lo = __builtin_amdgcn_alignbit(b, a, pos & 31);
         hi = __builtin_amdgcn_alignbit(c, b, pos & 31);
     }
@@ -315,9 +263,6 @@ __device__ __forceinline__ void tok_e(uint32_t lo, uint32_t hi, uint32_t e, uint
 // and the word after them loaded ahead, so the table read is the only LDS access on the chain; the
 // refill (one word when fewer than 32 bits are left, after the length part of a copy token too)
 // only consumes a word loaded a step earlier.  Same steps, same results as tok<false>.
-#ifndef NDFL_BITBUF
-#define NDFL_BITBUF 1
-#endif
 struct Bb {
     uint64_t buf;      // the bits from pos on (nb of them valid)
     uint32_t nb;       // 32..64 at a token's start
@@ -325,7 +270,7 @@ struct Bb {
     uint32_t nxt;      // that word
     uint32_t pos;      // round-relative bit position
 };
-// (V: the staged round in LDS (Lv) or the input in global memory (Gv): region word i = v.ld(i))
+// (V: the staged round in LDS (Lv): region word i = v.ld(i))
 template <class V>
 __device__ __forceinline__ void bb_init(Bb& b, const V& v, uint32_t pos) {
     const uint32_t i = (pos >> 5) - v.rw, s = pos & 31;
@@ -399,7 +344,6 @@ __device__ __forceinline__ void tok_bb(Bb& b, const V& v, const TT& t, bool empt
 // terminal token (true: end of block or an error, in tk).
 __device__ __forceinline__ bool run_to(const Lv& v, uint32_t& pos, const Tabs& t, bool ed, uint32_t stop, uint32_t nb,
                                        uint32_t& cnt, Tok& tk) {
-#if NDFL_BITBUF
     // the bit buffer up to the stop itself (pairs split there); only the input's last 48 bits go
     // through the checked decoder
     const uint32_t lim = min(stop, nb - min(nb, 48u));
@@ -413,13 +357,6 @@ __device__ __forceinline__ bool run_to(const Lv& v, uint32_t& pos, const Tabs& t
         } while (b.pos < lim);
         pos = b.pos;
     }
-#else
-    while (pos + 48 < stop) {
-        tok<false>(v, pos, t, ed, stop, nb, tk);
-        if (tk.kind > K_LEN) return true;
-        cnt += tk.n;
-    }
-#endif
     while (pos < stop) {
         tok<true>(v, pos, t, ed, stop, nb, tk);
         if (tk.kind > K_LEN) return true;
@@ -431,7 +368,7 @@ __device__ __forceinline__ bool run_to(const Lv& v, uint32_t& pos, const Tabs& t
 // ---- block header (lane 0) ----------------------------------------------------------------------
 // Parses the header at p into h and (dynamic) lens[0, numLit) and lens[288, 288 + numDist) (the
 // caller zeroes lens); validation in the reference's order up to END_OF_BLOCK_CODE_ZERO_LENGTH; the
-// tree checks of the two codes follow in build_code.  cl_tab: 128 u16 of scratch (LDS).
+// tree checks of the two codes follow in build_code_l.  cl_tab: 128 u16 of scratch (LDS).
 struct Hdr {
     uint64_t pos, d0;
     uint32_t err, bfinal, btype, len, numlit, numdist;
@@ -590,187 +527,16 @@ __device__ __forceinline__ void bsync() {
     if (WS) wsync(); else __syncthreads();
 }
 
-// Canonical code from S.lens[base .. base+n) into the primary table `prim` (pbits) and the
+// ---- table build -------------------------------------------------------------------------------
+// Canonical code from S.lens[base .. base+n) into the primary table `prim` (PB bits) and the
 // extension area `x` (cap words): second-level tables for the codes longer than the primary when
-// they fit, else the canonical slow-path arrays (wave).  Returns the tree check result of
-// codeLengthsToCodeTree (D/decomp/Open.java:705-756) (uniform).
-template <bool WS = false>
-__device__ int build_code(Shared& S, uint32_t base, uint32_t n, uint32_t* prim, uint32_t pbits, uint32_t* x,
-                          uint32_t cap, bool is_lit, int lane) {
-    for (uint32_t k = (uint32_t)lane; k < (1u << pbits); k += 64) prim[k] = 0;
-    uint32_t c[16];
-#pragma unroll
-    for (int l = 0; l < 16; l++) c[l] = 0;
-    uint32_t mylen[5], rank[5];
-    const uint64_t lt = (1ull << lane) - 1;
-#pragma unroll
-    for (int q = 0; q < 5; q++) {
-        const uint32_t s = (uint32_t)q * 64 + (uint32_t)lane;
-        const uint32_t l = (s < n) ? S.lens[base + s] : 0u;
-        mylen[q] = l;
-        rank[q] = 0;
-        if ((uint32_t)q * 64 < n) {
-#pragma unroll
-            for (int L = 1; L < 16; L++) {
-                const uint64_t m = __ballot(l == (uint32_t)L);
-                if (l == (uint32_t)L) rank[q] = c[L] + (uint32_t)__popcll(m & lt);
-                c[L] += (uint32_t)__popcll(m);
-            }
-        }
-    }
-    const int err = tree_check(c);
-    if (err) return err;
-    uint32_t fst[16], off[16];
-    {
-        uint32_t code = 0, o = 0;
-        fst[0] = 0; off[0] = 0;
-#pragma unroll
-        for (int l = 1; l < 16; l++) {
-            code = (code + (l > 1 ? c[l - 1] : 0)) << 1;
-            fst[l] = code; off[l] = o; o += c[l];
-        }
-    }
-    bsync<WS>();                            // prim zeroed
-    // the longest code under each primary prefix of the long codes (a canonical code's prefix set
-    // is prefix-free with the short codes, so these entries are free)
-#pragma unroll
-    for (int q = 0; q < 5; q++) {
-        const uint32_t l = mylen[q];
-        if (l <= pbits) continue;
-        uint32_t f = 0;
-#pragma unroll
-        for (int L = 1; L < 16; L++) if (l == (uint32_t)L) f = fst[L];
-        atomicMax(&prim[rev_bits((f + rank[q]) >> (l - pbits), pbits)], l);
-    }
-    bsync<WS>();
-    // second-level table offsets: exclusive scan of 2^(longest - pbits) over the primary entries
-    const uint32_t per = (1u << pbits) / 64;
-    uint32_t loc = 0;
-    for (uint32_t i = 0; i < per; i++) {
-        const uint32_t m = prim[(uint32_t)lane * per + i];
-        loc += m ? 1u << (m - pbits) : 0u;
-    }
-    uint32_t incl = loc;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += y;
-    }
-    const bool two = __shfl(incl, 63, 64) <= cap;
-    {
-        uint32_t o = incl - loc;
-        for (uint32_t i = 0; i < per; i++) {
-            const uint32_t k = (uint32_t)lane * per + i;
-            const uint32_t m = prim[k];
-            if (m) {
-                prim[k] = two ? ((o << 16) | ((m - pbits) << 5)) : 0u;
-                o += 1u << (m - pbits);
-            }
-        }
-    }
-    if (!two && lane < 16) {
-        uint16_t* first = (uint16_t*)(x + n + 16);
-        uint16_t* offv = first + 16;
-        first[lane] = (uint16_t)fst[lane];
-        offv[lane] = (uint16_t)off[lane];
-        uint32_t ll = 0;
-#pragma unroll
-        for (int L = 1; L < 16; L++) if (lane == L) ll = fst[L] + c[L];
-        x[n + lane] = lane ? (ll << (15 - lane)) : 0u;
-    }
-    bsync<WS>();
-#pragma unroll
-    for (int q = 0; q < 5; q++) {
-        const uint32_t l = mylen[q];
-        if (!l) continue;
-        const uint32_t s = (uint32_t)q * 64 + (uint32_t)lane;
-        uint32_t f = 0, o = 0;
-#pragma unroll
-        for (int L = 1; L < 16; L++) if (l == (uint32_t)L) { f = fst[L]; o = off[L]; }
-        const uint32_t ent = is_lit ? lit_entry(s, l) : dist_entry(s, l);
-        const uint32_t code = f + rank[q];
-        if (l <= pbits) {
-            if (l + 4 >= pbits)                 // (<= 16 entries; shorter codes: all lanes, below)
-                for (uint32_t k = rev_bits(code, l); k < (1u << pbits); k += (1u << l)) prim[k] = ent;
-        } else if (two) {
-            const uint32_t pe = prim[rev_bits(code >> (l - pbits), pbits)];
-            const uint32_t sb = pe >> 16, sd = (pe >> 5) & 15, r = l - pbits;
-            for (uint32_t k = rev_bits(code & ((1u << r) - 1u), r); k < (1u << sd); k += (1u << r)) x[sb + k] = ent;
-        }
-        if (!two) x[o + rank[q]] = ent;
-    }
-    // the codes shorter than pbits - 4 (more than 16 entries each, up to 2^(pbits-1)): one symbol at a
-    // time over all lanes, where a lane filling its own would hold the wave for its longest run
-#pragma unroll
-    for (int q = 0; q < 5; q++) {
-        if ((uint32_t)q * 64 >= n) continue;    // (uniform)
-        uint64_t sm = __ballot(mylen[q] != 0 && mylen[q] + 4 < pbits);
-        while (sm) {
-            const int src = (int)__builtin_ctzll(sm);
-            sm &= sm - 1;
-            const uint32_t l = (uint32_t)__builtin_amdgcn_readlane((int)mylen[q], src);
-            const uint32_t r = (uint32_t)__builtin_amdgcn_readlane((int)rank[q], src);
-            uint32_t f = 0;
-#pragma unroll
-            for (int L = 1; L < 16; L++) if (l == (uint32_t)L) f = fst[L];
-            const uint32_t sy = (uint32_t)q * 64 + (uint32_t)src;
-            const uint32_t ent = is_lit ? lit_entry(sy, l) : dist_entry(sy, l);
-            for (uint32_t k = rev_bits(f + r, l) + ((uint32_t)lane << l); k < (1u << pbits); k += 64u << l) prim[k] = ent;
-        }
-    }
-    bsync<WS>();
-    return 0;
-}
-
-// Literal pairs in the primary table: an entry whose code is a literal becomes
-// 1 << 31 | adv | l1 << 4 | pair << 8 | b1 << 9 | b2 << 17, with pair set when the next LB - l1 bits
-// start with a second literal code (its length l2 <= LB - l1) and adv = l1 + l2 for a pair, l1
-// otherwise -- an unchecked step adds adv with no select.
-template <bool WS = false>
-__device__ void group_lits(Tabs& t, int lane) {
-    uint32_t nv[(1u << LB) / 64];
-#pragma unroll
-    for (uint32_t q = 0; q < (1u << LB) / 64; q++) {
-        const uint32_t k = q * 64 + (uint32_t)lane;
-        const uint32_t e1 = t.lit[k];
-        const uint32_t l1 = e1 & 31;
-        uint32_t v = e1;
-        if (l1 && ((e1 >> 9) & 3) == K_LIT) {
-            const uint32_t b1 = (e1 >> 16) & 0xFFu;
-            v = (1u << 31) | l1 | (l1 << 4) | (b1 << 9);
-            const uint32_t e2 = t.lit[k >> l1];
-            const uint32_t l2 = e2 & 31;
-            if (l1 < LB && l2 && l1 + l2 <= LB && ((e2 >> 9) & 3) == K_LIT)
-                v = (1u << 31) | (l1 + l2) | (l1 << 4) | (1u << 8) | (b1 << 9) | (((e2 >> 16) & 0xFFu) << 17);
-        }
-        nv[q] = v;
-    }
-    bsync<WS>();
-#pragma unroll
-    for (uint32_t q = 0; q < (1u << LB) / 64; q++) t.lit[q * 64 + (uint32_t)lane] = nv[q];
-    bsync<WS>();
-}
-
-// Fixed code lengths (D/decomp/Open.java:812-830) into S.lens.
-__device__ void fixed_lens(Shared& S, int lane) {
-    for (uint32_t s = (uint32_t)lane; s < 320; s += 64) {
-        uint32_t l;
-        if (s < 288) l = s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : 8;
-        else l = 5;
-        S.lens[s] = (uint8_t)l;
-    }
-}
-
-// ---- table build, round 6 ---------------------------------------------------------------------
-// The same tables (word for word where a decoder reads them: scripts/r06/build_bench.hip compares
-// every header of a config-4 stream), built with a fraction of the instructions.  The build above
-// runs as a call from the decode passes and took ~33 K cycles for a literal/length code at one wave
-// per SIMD: its per-length arrays (counts, first codes, rank offsets) sat in scratch memory, indexed
-// by each lane's code length; its tree check compared 64-bit values in the vector unit; 15-way
-// select chains picked a lane's per-length values; codes were written one symbol at a time; and
-// every LDS access went through a generic pointer (a null check and a conversion per access, the
-// callee not knowing its arguments were LDS).  A single wave issues about one instruction per few
-// cycles, so the instruction count -- scalar ones included -- sets the time.  Here:
+// they fit, else the canonical slow-path arrays.  Returns the tree check result of
+// codeLengthsToCodeTree (D/decomp/Open.java:705-756) (uniform).  The build runs as a call from the
+// decode passes, on one wave, which issues about one instruction per few cycles, so the instruction
+// count -- scalar ones included -- sets the time (measured: the round-3 build, with its per-length
+// arrays in scratch memory, 15-way select chains, codes written one symbol at a time and generic
+// LDS pointers, took ~33 K cycles for a literal/length code at one wave per SIMD; scripts/r06/
+// build_bench.hip compared both builds word for word on every header of a config-4 stream):
 //   * LDS-typed pointers (address space 3) and the primary bits as a template parameter;
 //   * ranks bit-sliced: four ballots give each lane the mask of lanes whose length equals its own;
 //   * per-length values (rank offset O, first code F, O - F) in LDS, read by length (`scr`: 64 words
@@ -782,11 +548,8 @@ __device__ void fixed_lens(Shared& S, int lane) {
 //     [0, LJ[L]) of the MSB-first prefix space), the symbol from the code's rank, through the
 //     canonical entry array every symbol wrote into the extension area (x[O[l] + rank]: the slow
 //     path's array anyway);
-//   * the long codes' prefixes and second-level tables as before (the second level then overwrites
-//     that entry order in x).
-#ifndef NDFL_BUILD_V2
-#define NDFL_BUILD_V2 1
-#endif
+//   * the long codes' prefixes (atomic max of the longest code under each) and second-level tables
+//     (the second level then overwrites that entry order in x).
 typedef __attribute__((address_space(3))) uint32_t lu32;
 typedef __attribute__((address_space(3))) uint16_t lu16;
 typedef __attribute__((address_space(3))) uint8_t lu8;
@@ -798,8 +561,8 @@ __device__ unsigned long long g_bprof[8192 * 8];      // per wave (block) and se
 #else
 #define BPROF(i) do { } while (0)
 #endif
-// GROUP (a dynamic literal/length code): literal pairs joined into the primary entries as group_lits
-// does, from the pulled entries still in registers
+// GROUP (a dynamic literal/length code): literal pairs joined into the primary entries, from the
+// pulled entries still in registers
 template <bool WS, uint32_t PB, bool GROUP = false>
 __device__ __forceinline__ int build_code_l(LShared* S, uint32_t base, uint32_t n, lu32* prim, lu32* x, uint32_t cap,
                                             bool is_lit, int lane, lu32* scr) {
@@ -883,7 +646,7 @@ __device__ __forceinline__ int build_code_l(LShared* S, uint32_t base, uint32_t 
     bool two = true;
     if (maxl > PB) {
         // the longest code under each primary prefix of the long codes (prefix-free with the short
-        // codes, so these entries are free), then the second-level offsets (as build_code)
+        // codes, so these entries are free), then the second-level offsets
 #pragma unroll
         for (uint32_t k = (uint32_t)lane * 4; k < (1u << PB); k += 256) *(lu128*)&prim[k] = u32x4{0u, 0u, 0u, 0u};
         bsync<WS>();
@@ -938,8 +701,10 @@ __device__ __forceinline__ int build_code_l(LShared* S, uint32_t base, uint32_t 
         for (uint32_t i = 0; i < PER; i++)
             if (cv[i] < lj[PB]) prim[i * 64 + (uint32_t)lane] = d[i];
         if (GROUP) {
-            // literal pairs (group_lits): an entry whose code is a literal becomes
-            // 1 << 31 | adv | l1 << 4 | pair << 8 | b1 << 9 | b2 << 17 (see there); a long prefix's
+            // literal pairs: an entry whose code is a literal becomes
+            // 1 << 31 | adv | l1 << 4 | pair << 8 | b1 << 9 | b2 << 17, with pair set when the next
+            // PB - l1 bits start with a second literal code (l2 <= PB - l1) and adv = l1 + l2 for a pair,
+            // l1 otherwise -- an unchecked step adds adv with no select; a long prefix's
             // entry (length field 0) stays
             bsync<WS>();
             uint32_t v[PER];
@@ -1021,34 +786,9 @@ __device__ __noinline__ int build_tables_l(LShared* S, int lane, lu32* scr) {
 // words of LDS the build may use (the round stage: nothing is staged while a block's tables are built).
 template <bool WS = false>
 __device__ __forceinline__ int build_tables(Shared& S, int lane, bool& empty_dist, uint32_t* scr) {
-#if NDFL_BUILD_V2
     const int r = build_tables_l<WS>((LShared*)&S, lane, (lu32*)scr);
     empty_dist = (r & 0x100) != 0;
     return r & 0xFF;
-#else
-    (void)scr;
-    empty_dist = false;
-    if (S.h_btype == 1) {
-        fixed_lens(S, lane);
-        bsync<WS>();
-        build_code<WS>(S, 0, 288, S.t.lit, LB, S.t.lx, LX, true, lane);
-        build_code<WS>(S, 288, 32, S.t.dst, DB, S.t.dx, DX, false, lane);
-        return 0;
-    }
-    const uint32_t numDist = S.h_numdist;
-    int e = build_code<WS>(S, 0, 288, S.t.lit, LB, S.t.lx, LX, true, lane);
-    if (e) return e;
-    group_lits<WS>(S.t, lane);
-    // distance code: empty (one zero length) or one used code padded at index 31 (:398-425)
-    const uint32_t dl = (lane < 32) ? S.lens[288 + lane] : 0u;
-    empty_dist = numDist == 1 && S.lens[288] == 0;
-    if (empty_dist) return 0;
-    const uint32_t ones = (uint32_t)__popcll(__ballot(dl == 1)), other = (uint32_t)__popcll(__ballot(dl > 1));
-    bsync<WS>();
-    if (ones == 1 && other == 0 && lane == 0) S.lens[288 + 31] = 1;
-    bsync<WS>();
-    return build_code<WS>(S, 288, 32, S.t.dst, DB, S.t.dx, DX, false, lane);
-#endif
 }
 
 // ---- segmented speculative decode of one round ------------------------------------------------
@@ -1071,15 +811,12 @@ __device__ __forceinline__ int build_tables(Shared& S, int lane, bool& empty_dis
 // sweeps re-ran from its exact start and still missed its speculation; fewer, isolated failures are
 // resolved by the fix-up sweeps alone (round 5: frontier trigger 1 -> 4, count 10.8 -> 10.2 ms: the
 // 4-byte-periodic binary tables miss ~20 % of their lanes, which two or three sweeps fix for less
-// than 7 phase runs cost).  NDFL_FIX_SERIAL=1 restores the in-order fix-up loop (A/B).
+// than 7 phase runs cost).
 #ifndef NDFL_PH_FALLBACK
 #define NDFL_PH_FALLBACK 8
 #endif
 #ifndef NDFL_PH_FRONTIER
 #define NDFL_PH_FRONTIER 4      // frontier misses (one per sweep) before the phase runs are decoded
-#endif
-#ifndef NDFL_FIX_SERIAL
-#define NDFL_FIX_SERIAL 0
 #endif
 #ifndef NDFL_XCP2
 #define NDFL_XCP2 192           // (round 5: 1024, i.e. the segment end -> 192 with the end compared as a
@@ -1245,25 +982,6 @@ __device__ void round_decode(const In& in, const Tabs& t, bool ed, uint64_t rs, 
         if (nph > 1) phase_runs(j0);
         S.exit_[lane] = r.end;
         if (pc) { const uint64_t x = wall_clock64(); pc->phases += x - tk0; tk0 = x; }
-#if NDFL_FIX_SERIAL
-        S.kind_[lane] = r.kind;
-        __syncthreads();
-        first_term = (r.kind != T_EXIT && (uint32_t)lane == j0) ? j0 : 64u;
-        first_term = __shfl(first_term, (int)j0, 64);
-        for (uint32_t j = j0 + 1; j < 64 && first_term == 64; j++) {
-            nfix++;
-            if ((uint32_t)lane == j) {
-                const uint32_t st = (uint32_t)S.exit_[j - 1];
-                if (!(fin && st == r.start)) {
-                    verify_run(v, t, ed, nb, st, s, C1, C2, e, p0, ph, lane, nph, r);
-                    S.exit_[lane] = r.end;
-                    S.kind_[lane] = r.kind;
-                }
-            }
-            __syncthreads();
-            if (S.kind_[j] != T_EXIT) first_term = j;
-        }
-#else
         // Fix-up sweeps: every lane after j0 whose start is not its predecessor's current exit
         // re-runs its verify from that exit, all such lanes at once.  A lane whose start equals its
         // predecessor's exit holds the exact result for that start (a synchronised run ends in its
@@ -1302,7 +1020,6 @@ __device__ void round_decode(const In& in, const Tabs& t, bool ed, uint64_t rs, 
             __syncthreads();                    // every lane has read its predecessor's exit
             if (redo) S.exit_[lane] = r.end;
         }
-#endif
         if (pc) { const uint64_t x = wall_clock64(); pc->serial += x - tk0; tk0 = x; }
     }
     out.start = g.base + r.start; out.end = g.base + r.end; out.cnt = r.cnt;
@@ -1319,18 +1036,11 @@ __device__ void round_decode(const In& in, const Tabs& t, bool ed, uint64_t rs, 
 #define NDFL_PHASE_SWITCH 48   // lanes of a round that failed to synchronise before the block's next
 #endif                         // rounds are phase-mapped (measured: 4-16 much slower; 32 -> 48: config 2
                                // count 16.9 -> 9.5 ms, fixed-Huffman text resyncs through the 8-phase verify)
-#ifndef NDFL_PHASE_JUMP
-#define NDFL_PHASE_JUMP 1      // phase runs step four 8-bit literals at once where they can
-#endif
-#ifndef NDFL_PHASE_ESC
-#define NDFL_PHASE_ESC 1       // escape-prefix literal blocks: phase runs step to the next escape byte
-#endif
-#ifndef NDFL_PHASE_GROUP
-#define NDFL_PHASE_GROUP 2     // phase runs decoded together (1, 2, 4 or 8; round 3, one token a step:
-#endif                         // 1: 14.6, 2: 13.9, 4: 12.9, 8: 12.8 ms count pass; round 5, four 8-bit
-                               // literals a step: 8 / 4 / 2: 10.35 / 9.57 / 9.46 against 10.0 ms without
-                               // the four-literal step, random-data count pass 7.5 -> 6.5 ms per GiB,
-                               // profiles/r05_ab_phase_jump.txt)
+// Phase runs step four 8-bit literals at once where they can, and in escape-prefix literal blocks
+// to the next escape byte; two of them are decoded together (G below; measured, count pass: round 3,
+// one token a step: 1: 14.6, 2: 13.9, 4: 12.9, 8: 12.8 ms; round 5, four 8-bit literals a step:
+// 8 / 4 / 2: 10.35 / 9.57 / 9.46 against 10.0 ms without the four-literal step, random-data count
+// pass 7.5 -> 6.5 ms per GiB, profiles/r05_ab_phase_jump.txt)
 
 // count run from st to the first token boundary at or past e (or the block end); the first step is
 // a single token whose end and bytes are returned in fb / fbc (fb = NOCP: none)
@@ -1381,7 +1091,6 @@ __device__ __forceinline__ void phase_multi(const Lv& v, const Tabs& t, bool ed,
 #pragma unroll
         for (int k = 0; k < N; k++) { f[k] = l[k] && p[k] + 48 < e; any = any || f[k]; }
         if (!any) break;
-#if NDFL_PHASE_JUMP
         // a run's next four tokens are looked up at once, at p, p+8, p+16, p+24 (independent reads):
         // when all four are literal entries of 8 bits (one 8-bit code, or a pair of 8 bits), the run
         // moves 32 bits in one step -- phase-locked codes are mostly 8-bit literals (random data:
@@ -1418,34 +1127,6 @@ __device__ __forceinline__ void phase_multi(const Lv& v, const Tabs& t, bool ed,
                 else c[k] += tk.n;
             }
         }
-#else
-        // each run's window is its low word pair only; the third word (for a length/distance token's
-        // distance bits) is read in the rare non-literal branch -- phase-locked codes are literals
-        uint32_t lo[N], wb[N], en[N];
-#pragma unroll
-        for (int k = 0; k < N; k++) {
-            const uint32_t pp = f[k] ? p[k] : p[0];
-            const uint32_t* qk = v.p + ((pp >> 5) - v.rw) * 64;
-            const uint32_t a = qk[0];
-            wb[k] = qk[64];
-            lo[k] = __builtin_amdgcn_alignbit(wb[k], a, pp & 31);
-        }
-#pragma unroll
-        for (int k = 0; k < N; k++) en[k] = t.lit[lo[k] & ((1u << LB) - 1u)];
-#pragma unroll
-        for (int k = 0; k < N; k++) {
-            const bool q = f[k] && (en[k] >> 31);
-            if (q) { p[k] += en[k] & 15; c[k] += 1u + ((en[k] >> 8) & 1u); }
-            if (f[k] && !q) {
-                Tok tk;
-                const uint32_t cw = v.p[((p[k] >> 5) - v.rw) * 64 + 128];
-                const uint32_t hi = __builtin_amdgcn_alignbit(cw, wb[k], p[k] & 31);
-                tok_e<false>(lo[k], hi, en[k], p[k], t, ed, e, nb, tk);
-                if (tk.kind > K_LEN) { l[k] = false; O[k].kr = tk.kind == K_EOB ? (T_EOB << 5) : ((T_ERR << 5) | tk.val); }
-                else c[k] += tk.n;
-            }
-        }
-#endif
     }
 #pragma unroll
     for (int k = 0; k < N; k++) {
@@ -1563,8 +1244,7 @@ __device__ __noinline__ void round_decode_phased(const In& in, const Tabs& t, bo
     // the 8 runs' results stay in registers (a lane reads back only its own, through sel8)
     uint32_t endv[8], cntv[8], fbcv[8], krv[8];
     uint32_t fbl = 0, fbh = 0;
-#if NDFL_PHASE_GROUP > 1
-    constexpr uint32_t G = NDFL_PHASE_GROUP >= 8 ? 8 : NDFL_PHASE_GROUP >= 4 ? 4 : 2;
+    constexpr uint32_t G = 2;                   // phase runs decoded together
     // (one copy of each run group's code, its results selected into place: the loop unrolled made the
     // function 74 KB, more than the instruction cache, with the pass's other code competing)
 #pragma unroll 1
@@ -1586,21 +1266,6 @@ __device__ __noinline__ void round_decode_phased(const In& in, const Tabs& t, bo
             if (g < 4) fbl |= fo << (8 * g); else fbh |= fo << (8 * (g - 4));
         }
     }
-#else
-    for (uint32_t f = 0; f < 8; f++) {
-        uint32_t en, cn, kr, fb, fbc;
-        phase_run(v, t, ed, nb, s + f, e, en, cn, kr, fb, fbc);      // (past e: empty, ends at s + f)
-#pragma unroll
-        for (uint32_t k = 0; k < 8; k++) {
-            endv[k] = k == f ? en : endv[k];
-            cntv[k] = k == f ? cn : cntv[k];
-            fbcv[k] = k == f ? fbc : fbcv[k];
-            krv[k] = k == f ? kr : krv[k];
-        }
-        const uint32_t fo = (fb != NOCP && fb - s < 255u) ? fb - s : 255u;
-        if (f < 4) fbl |= fo << (8 * f); else fbh |= fo << (8 * (f - 4));
-    }
-#endif
     // map of lane j: phase of lane j-1 -> phase of lane j
     uint32_t Q = 0;                             // lane 0: always phase 0
 #pragma unroll
@@ -1739,33 +1404,23 @@ typedef __attribute__((address_space(1))) uint64_t gu64;
 #else
 #define NDFL_OA(x) (x)
 #endif
-// NDFL_EMIT_W16: completed literal words are held (up to 3) and leave as one 16-byte store, so a lane
-// issues a quarter of the scattered stores (each store instruction of a wave touches 64 lines)
-#ifndef NDFL_EMIT_W16
-#define NDFL_EMIT_W16 1
-#endif
-#ifndef NDFL_EMIT_NT
-#define NDFL_EMIT_NT 0          // (A/B: non-temporal 16-byte literal stores)
-#endif
+// Completed literal words are held (up to 3) and leave as one 16-byte store, so a lane issues a
+// quarter of the scattered stores (each store instruction of a wave touches 64 lines).  (Measured:
+// non-temporal 16-byte literal stores, emit 8.0 -> 11.6 ms.)
 typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(1))) u32x4v gu128;
 struct Wr {
     uint64_t acc;               // pending literal bytes (low byte first)
     uint32_t an;                // pending byte count (0..3 between tokens)
     uint64_t dst;               // output address of acc's first byte
-#if NDFL_EMIT_W16
     uint32_t q0, q1, q2, hn;    // completed words held back (hn of them), at dst - 4 hn
-#endif
 };
 __device__ __forceinline__ void wr_init(Wr& w, uint64_t dst) {
     w.acc = 0; w.an = 0; w.dst = dst;
-#if NDFL_EMIT_W16
     w.q0 = 0; w.q1 = 0; w.q2 = 0; w.hn = 0;
-#endif
 }
 // held words out (before a copy or at the end)
 __device__ __forceinline__ void wr_drain(Wr& w, gu8* out) {
-#if NDFL_EMIT_W16
     if (w.hn) {
         gu8* d = out + NDFL_OA(w.dst - 4 * w.hn);
         if (w.hn >= 2) *(gu64*)d = (uint64_t)w.q0 | ((uint64_t)w.q1 << 32);
@@ -1773,22 +1428,14 @@ __device__ __forceinline__ void wr_drain(Wr& w, gu8* out) {
         if (w.hn == 3) *(gu32*)(d + 8) = w.q2;
         w.hn = 0;
     }
-#else
-    (void)w; (void)out;
-#endif
 }
 __device__ __forceinline__ void wr_lit(Wr& w, gu8* out, uint32_t val, uint32_t n) {
     w.acc |= (uint64_t)val << (8 * w.an);
     w.an += n;
     if (w.an >= 4) {
         const uint32_t word = (uint32_t)w.acc;
-#if NDFL_EMIT_W16
         if (w.hn == 3) {
-#if NDFL_EMIT_NT
-            __builtin_nontemporal_store(u32x4v{w.q0, w.q1, w.q2, word}, (gu128*)(out + NDFL_OA(w.dst - 12)));
-#else
             *(gu128*)(out + NDFL_OA(w.dst - 12)) = u32x4v{w.q0, w.q1, w.q2, word};
-#endif
             w.hn = 0;
         } else {
             w.q0 = w.hn == 0 ? word : w.q0;
@@ -1796,9 +1443,6 @@ __device__ __forceinline__ void wr_lit(Wr& w, gu8* out, uint32_t val, uint32_t n
             w.q2 = w.hn == 2 ? word : w.q2;
             w.hn++;
         }
-#else
-        *(gu32*)(out + NDFL_OA(w.dst)) = word;
-#endif
         w.acc >>= 32;
         w.an -= 4;
         w.dst += 4;
@@ -1834,7 +1478,6 @@ __device__ __forceinline__ void wr_copy(gu8* out, uint64_t dst, uint32_t len, ui
         // a run: 16-byte stores (the last one overlapping back), so the wave's store loop takes
         // at most 17 trips for the longest run instead of 65
         const uint32_t v4 = lastb * 0x01010101u;
-#if NDFL_EMIT_W16
         if (len >= 16) {
             const u32x4v x = {v4, v4, v4, v4};
             uint32_t k = 0;
@@ -1842,7 +1485,6 @@ __device__ __forceinline__ void wr_copy(gu8* out, uint64_t dst, uint32_t len, ui
             if (k < len) *(gu128*)(d + len - 16) = x;
             return;
         }
-#endif
         if (len >= 4) {
             uint32_t k = 0;
             for (; k + 4 <= len; k += 4) *(gu32*)(d + k) = v4;
@@ -1852,7 +1494,6 @@ __device__ __forceinline__ void wr_copy(gu8* out, uint64_t dst, uint32_t len, ui
         }
         return;
     }
-#if NDFL_EMIT_W16
     if (dist >= 16 && len >= 16) {
         uint32_t k = 0;
         u32x4v x = {0, 0, 0, 0};
@@ -1861,7 +1502,6 @@ __device__ __forceinline__ void wr_copy(gu8* out, uint64_t dst, uint32_t len, ui
         lastb = x.w >> 24;
         return;
     }
-#endif
     if (dist >= 8 && len >= 8) {
         uint32_t k = 0;
         uint64_t x = 0;
@@ -1938,12 +1578,6 @@ ndfl_inflate_hdr_kernel(const uint32_t* w, uint64_t nwords, uint64_t nbits, cons
 // round's staged input.
 #ifndef NDFL_COUNT_WPE
 #define NDFL_COUNT_WPE 3
-#endif
-#ifndef NDFL_REC_BATCH
-#define NDFL_REC_BATCH 16       // round records claimed per atomic (the pool keeps 65,536 spare)
-#endif
-#ifndef NDFL_TREC_BATCH
-#define NDFL_TREC_BATCH 4       // table records claimed per atomic
 #endif
 namespace wv {
 // ---- escape-prefix literal blocks, one lane per block (round 6) ------------------------------------
@@ -2023,27 +1657,11 @@ __device__ __forceinline__ uint32_t count_flat_group(const In& in, const uint32_
         uint32_t brec = NOREC;
         if (!te) {
             if (c < pool.nslot && pool.nbt) {
-                if (tb_next >= tb_end) {
-                    uint32_t b = 0;
-                    if (lane == 0) b = atomicAdd(pool.bctr, (uint32_t)NDFL_TREC_BATCH);
-                    b = __builtin_amdgcn_readfirstlane(b);
-                    tb_next = b; tb_end = b + NDFL_TREC_BATCH;
-                }
-                brec = tb_next++;
-                if (brec < pool.nbt) {
-                    uint4* dst = (uint4*)(pool.bt + (uint64_t)brec * BT_BYTES);
-                    const uint4* src = (const uint4*)&S.t;
-                    for (uint32_t q = (uint32_t)lane; q < sizeof(Tabs) / 16; q += 64) dst[q] = src[q];
-                    if (lane == 0) {
-                        uint64_t* h = (uint64_t*)(pool.bt + (uint64_t)brec * BT_BYTES + sizeof(Tabs));
-                        h[0] = cands[c]; h[1] = S.h_d0;
-                        uint32_t* h32 = (uint32_t*)(h + 2);
-                        h32[0] = S.h_bfinal; h32[1] = S.h_btype; h32[2] = ed ? 1u : 0u;
-                        h32[3] = ((1u << (8 - kk)) - 1u) * 0x01010101u;    // (the escape prefix mask)
-                    }
-                } else {
-                    brec = NOREC;
-                }
+                brec = claim_table_record(pool, tb_next, tb_end, lane);
+                if (brec != NOREC)
+                    write_table_record(pool, brec, S.t, cands[c], S.h_d0, S.h_bfinal, S.h_btype, ed,
+                                       ((1u << (8 - kk)) - 1u) * 0x01010101u,      // (the escape prefix mask)
+                                       (uint32_t)lane, 64);
             }
             const TabsG tg{S.t.lit, S.t.dst, S.t.lx, S.t.dx};
             escs[k * 64 + lane] = (uint8_t)flat_esc_entry(tg, kk, (uint32_t)lane);
@@ -2114,7 +1732,7 @@ __device__ __forceinline__ uint32_t count_flat_group(const In& in, const uint32_
         uint32_t base = 0, r0 = 0, re = 0, per = 0, pw = 0, nbr = 0, idx = NOREC, j = 0, p = 0, jst = 0, bytes = 0, sn = 0;
         uint64_t* ps = nullptr;                         // the round record's starts and counts, its meta
         uint32_t* pc = nullptr;
-        uint4* mq = nullptr;
+        SegMeta* mp = nullptr;
         uint32_t* link = pool.head + my_c;              // where the next round record's index goes
         uint32_t st = 0;                                // 0 a round starts at pos, 1 in a round, 2 EOB, 3 back
         // the group is the pass's longest job: it takes the SIMD's issue slots first
@@ -2126,27 +1744,15 @@ __device__ __forceinline__ uint32_t count_flat_group(const In& in, const uint32_
                 ps[j] = o64 + base + jst;
                 pc[j] = bytes;
                 for (uint32_t jj = j + 1; jj < 64; jj++) { ps[jj] = ex; pc[jj] = 0; }
-                // (the fields as two 16-byte and one 8-byte stores of values at hand: a SegMeta built in
-                // registers was partly spilled, and its reload waited for the rings' loads in flight)
                 uint32_t kf = eob ? (uint32_t)T_EOB : (uint32_t)T_EXIT;
                 asm volatile("" : "+v"(kf));            // (materialised here, not a spilled constant)
-                mq[0] = make_uint4(eob ? j : 64u, kf, 0u, NOREC);
-                mq[1] = make_uint4((uint32_t)ex, (uint32_t)(ex >> 32), (uint32_t)ex, (uint32_t)(ex >> 32));
-                *(uint2*)(mq + 2) = make_uint2(pw, brec);
-                *(uint64_t*)((uint2*)(mq + 2) + 1) = o64 + base + r0;
+                write_round_meta(mp, eob ? j : 64u, kf, 0u, NOREC, ex, ex, pw, brec, o64 + base + r0);
                 *link = idx;                            // (the chain's head, then the previous round's next)
-                link = (uint32_t*)mq + 3;
+                link = &mp->next;
                 brec = NOREC;                           // (only the block's first round names its tables)
             }
             total += bytes;
             pos = base + p;
-        };
-        // segment j's record, and the next segment's start
-        auto next_seg = [&]() {
-            if (ps) { ps[j] = o64 + base + jst; pc[j] = bytes; }
-            total += bytes;
-            j++; jst = p; bytes = 0;
-            sn = j < 63 ? min(r0 + (j + 1) * per, re) : re;
         };
 #ifdef NDFL_FLAT_PROF
         unsigned long long fp_ph = 0, fp_t0 = clock64(), fp_n = 0;
@@ -2188,7 +1794,7 @@ __device__ __forceinline__ uint32_t count_flat_group(const In& in, const uint32_
                     if (E <= rsa) E = rsa + 1;
                     base = pos & ~31u;
                     r0 = pos - base; re = (uint32_t)(E - o64) - base;
-                    pw = max((uint32_t)NDFL_PW_MIN, ((re - r0 + 63) / 64 + 31) / 32); per = pw * 32;
+                    pw = seg_pw(re - r0); per = pw * 32;
                     nbr = nbo - min(nbo, base);
                     idx = NOREC;
                     if (recording) {
@@ -2201,9 +1807,9 @@ __device__ __forceinline__ uint32_t count_flat_group(const In& in, const uint32_
                     }
                     ps = idx != NOREC ? pool.start + (uint64_t)idx * 64 : nullptr;
                     pc = idx != NOREC ? pool.cnt + (uint64_t)idx * 64 : nullptr;
-                    mq = idx != NOREC ? (uint4*)(pool.meta + idx) : nullptr;
+                    mp = idx != NOREC ? pool.meta + idx : nullptr;
                     j = 0; p = r0; jst = r0; bytes = 0;
-                    sn = min(r0 + per, re);
+                    sn = seg_end(r0, per, re, 0);
                     st = 1;                             // (and the round's first step at once)
                 }
                 if (st != 1) continue;
@@ -2238,8 +1844,7 @@ __device__ __forceinline__ uint32_t count_flat_group(const In& in, const uint32_
                     if (my_brec == NOREC || ++others > NDFL_FLAT_OTHER_MAX) {
                         st = 3; why = 2;
                     } else {
-                        const uint32_t* tb = (const uint32_t*)(pool.bt + (uint64_t)my_brec * BT_BYTES);
-                        const TabsG tg{tb, tb + (1u << LB), tb + offsetof(Tabs, lx) / 4, tb + offsetof(Tabs, dx) / 4};
+                        const TabsG tg = tabs_view(tabrec(pool, my_brec));
                         uint32_t pp = 0;
                         Tok tk;
                         tok_e<true>(lo, hi, tg.lit[lo & ((1u << LB) - 1u)], pp, tg, my_ed, sn - p, nbr - min(nbr, p), tk);
@@ -2262,7 +1867,7 @@ __device__ __forceinline__ uint32_t count_flat_group(const In& in, const uint32_
                     j += sw ? 1u : 0u;
                     jst = sw ? p : jst;
                     bytes = sw ? 0u : bytes;
-                    sn = sw ? (j < 63 ? min(r0 + (j + 1) * per, re) : re) : sn;
+                    sn = sw ? seg_end(r0, per, re, j) : sn;
                 }
             }
         }
@@ -2337,10 +1942,10 @@ ndfl_inflate_count_wave_kernel(const uint32_t* w, uint64_t nwords, uint64_t nbit
             const uint32_t g0 = tk * 64;
             const uint64_t tf0 = stats ? wall_clock64() : 0;
             nredo = count_flat_group(in, flist + g0, min(64u, nfl - g0), cands, ncand, limit, stop_all, res, pool, hrec,
-                                     S, stg.w, lane, s_redo, tb_next, tb_end, stats ? ticket + 10 : nullptr);
-            if (stats && lane == 0) {                   // (ticket words 5, 6: chains sent back, group wave time)
-                atomicAdd(ticket + 5, nredo);
-                atomicAdd((unsigned long long*)(ticket + 6), (unsigned long long)(wall_clock64() - tf0));
+                                     S, stg.w, lane, s_redo, tb_next, tb_end, stats ? ticket + CT_FLAT_WHY : nullptr);
+            if (stats && lane == 0) {                   // (chains sent back, group wave time)
+                atomicAdd(ticket + CT_FLAT_REDO, nredo);
+                atomicAdd((unsigned long long*)(ticket + CT_FLAT_TIME64), (unsigned long long)(wall_clock64() - tf0));
             }
             continue;
         }
@@ -2410,32 +2015,15 @@ ndfl_inflate_count_wave_kernel(const uint32_t* w, uint64_t nwords, uint64_t nbit
                 n8 += (uint32_t)__popcll(__ballot(sy < 288 && S.lens[sy] == 8));
             }
             phased = n8 >= 192;
-            if (phased && NDFL_PHASE_ESC) esc4 = flat8_mask(S.t, lane);
+            if (phased) esc4 = flat8_mask(S.t, lane);
         }
         // the block's tables and header fields for the emit pass (a table record)
         uint32_t brec = NOREC;
         if (recording && pool.nbt) {
-            if (tb_next >= tb_end) {
-                uint32_t b = 0;
-                if (lane == 0) b = atomicAdd(pool.bctr, (uint32_t)NDFL_TREC_BATCH);
-                b = __builtin_amdgcn_readfirstlane(b);
-                tb_next = b; tb_end = b + NDFL_TREC_BATCH;
-            }
-            brec = tb_next++;
-            if (brec < pool.nbt) {
-                uint4* dst = (uint4*)(pool.bt + (uint64_t)brec * BT_BYTES);
-                const uint4* src = (const uint4*)&S.t;
-                for (uint32_t q = (uint32_t)lane; q < sizeof(Tabs) / 16; q += 64) dst[q] = src[q];
-                if (lane == 0) {
-                    uint64_t* h = (uint64_t*)(pool.bt + (uint64_t)brec * BT_BYTES + sizeof(Tabs));
-                    h[0] = cur; h[1] = d0;
-                    uint32_t* h32 = (uint32_t*)(h + 2);
-                    h32[0] = S.h_bfinal; h32[1] = S.h_btype; h32[2] = ed ? 1u : 0u;
-                    h32[3] = phased ? (esc4 ? esc4 : 1u) : 0u;      // (emit: 4-literal steps / escape scan)
-                }
-            } else {
-                brec = NOREC;
-            }
+            brec = claim_table_record(pool, tb_next, tb_end, lane);
+            if (brec != NOREC)
+                write_table_record(pool, brec, S.t, cur, d0, S.h_bfinal, S.h_btype, ed, tab_phase(phased, esc4),
+                                   (uint32_t)lane, 64);
         }
         if (pc) { const uint64_t x = wall_clock64(); pc->build += x - tb; tb = x; }
         uint64_t rs = d0;
@@ -2475,10 +2063,12 @@ ndfl_inflate_count_wave_kernel(const uint32_t* w, uint64_t nwords, uint64_t nbit
                     const int src = ft < 64 ? (int)ft : 63;
                     const uint64_t fe = __shfl((unsigned long long)r.end, src, 64);
                     const uint32_t fk = __shfl(r.kind, src, 64), fr = __shfl(r.reason, src, 64);
+                    // (the claim above and this record by hand, not claim_wave / write_round_meta /
+                    // link_round: with them this kernel spills one more register than it may)
                     if (lane == 0) {
                         SegMeta m;
                         m.ft = ft; m.kind_ft = fk; m.reason_ft = fr; m.next = NOREC;
-                        m.end_ft = fe; m.exit63 = fe; m.pw = g.pw; m.pad = brec; m.rs = g.base + g.r0;
+                        m.end_ft = fe; m.exit63 = fe; m.pw = g.pw; m.brec = brec; m.rs = g.base + g.r0;
                         pool.meta[idx] = m;
                         if (prev_rec == NOREC) pool.head[slot_base + c] = idx;
                         else pool.meta[prev_rec].next = idx;
@@ -2516,8 +2106,8 @@ ndfl_inflate_count_wave_kernel(const uint32_t* w, uint64_t nwords, uint64_t nbit
         o.bnd_bit = 0; o.bnd_cnt = 0;
         res[c] = o;
         if (stats) {
-            atomicAdd(&stats[0], nslow); atomicAdd(&stats[1], nfix); atomicAdd(&stats[2], nround);
-            unsigned long long* st64 = (unsigned long long*)(stats + 32);
+            atomicAdd(&stats[SW_NSLOW], nslow); atomicAdd(&stats[SW_NFIX], nfix); atomicAdd(&stats[SW_NROUND], nround);
+            unsigned long long* st64 = (unsigned long long*)(stats + SW_CLOCK64);
             atomicAdd(&st64[0], pcl.hdr); atomicAdd(&st64[1], pcl.spec); atomicAdd(&st64[2], pcl.verify);
             atomicAdd(&st64[3], pcl.phases); atomicAdd(&st64[4], pcl.serial); atomicAdd(&st64[5], pcl.rec);
             atomicAdd(&st64[6], pcl.build); atomicAdd(&st64[7], pcl.phmap);
@@ -2526,7 +2116,7 @@ ndfl_inflate_count_wave_kernel(const uint32_t* w, uint64_t nwords, uint64_t nbit
     }
     }
     if (stats && lane == 0) {                   // wave occupancy of the pass: busy sum, first start, last end
-        unsigned long long* st64 = (unsigned long long*)(stats + 32);
+        unsigned long long* st64 = (unsigned long long*)(stats + SW_CLOCK64);
         const uint64_t t_end = wall_clock64();
         atomicAdd(&st64[8], t_end - t_begin);
         atomicMax(&st64[9], t_end);
@@ -2580,27 +2170,23 @@ ndfl_inflate_emit_wave_kernel(const uint32_t* w, uint64_t nwords, uint64_t nbits
     uint64_t endpos = ch.start_bit;
     uint32_t nslow = 0, nfix = 0;
     uint32_t rec = ch.slot < pool.nslot ? pool.head[ch.slot] : NOREC;
-    // the next round's record is loaded one round ahead (its loads overlap this round's decode)
     SegMeta pm = {};
     uint64_t pst = 0;
     uint32_t pcn = 0;
-    if (rec != NOREC) { pm = pool.meta[rec]; pst = pool.start[(uint64_t)rec * 64 + lane]; pcn = pool.cnt[(uint64_t)rec * 64 + lane]; }
+    rec_fetch(pool, rec, lane, pm, pst, pcn);
     uint64_t bnd_bit = cur, bnd_out = base;     // start of the current block (partial-input decodes)
     for (int blk = 0;; blk++) {
         if (blk > 0 && cur == ch.end_bit) { status = ST_BOUNDARY; endpos = cur; break; }
         bnd_bit = cur; bnd_out = base;
         // the count pass's tables of this block, when its first round record names them
-        const char* btr = (rec != NOREC && pm.pad < pool.nbt) ? pool.bt + (uint64_t)pm.pad * BT_BYTES : nullptr;
-        if (btr && *(const uint64_t*)(btr + sizeof(Tabs)) != cur) btr = nullptr;     // (not this block)
+        const TabRec* btr = block_tables(pool, rec, pm, cur);
         if (btr) {
             __syncthreads();                    // the previous block's table reads are done
-            const uint4* src = (const uint4*)btr;
+            const uint4* src = (const uint4*)&btr->t;
             uint4* dst = (uint4*)&S.t;
             for (uint32_t q = (uint32_t)lane; q < sizeof(Tabs) / 16; q += 64) dst[q] = src[q];
             if (lane == 0) {
-                const uint64_t* h = (const uint64_t*)(btr + sizeof(Tabs));
-                const uint32_t* h32 = (const uint32_t*)(h + 2);
-                S.h_err = 0; S.h_d0 = h[1]; S.h_bfinal = h32[0]; S.h_btype = h32[1]; S.h_len = h32[2];
+                S.h_err = 0; S.h_d0 = btr->data_bit; S.h_bfinal = btr->bfinal; S.h_btype = btr->btype; S.h_len = btr->ed;
             }
             __syncthreads();
         } else {
@@ -2646,11 +2232,8 @@ ndfl_inflate_emit_wave_kernel(const uint32_t* w, uint64_t nwords, uint64_t nbits
                 r.start = pst;
                 r.cnt = pcn;
                 rec = m.next;
-                if (rec != NOREC) { pm = pool.meta[rec]; pst = pool.start[(uint64_t)rec * 64 + lane]; pcn = pool.cnt[(uint64_t)rec * 64 + lane]; }
-                const uint64_t nx = __shfl_down((unsigned long long)r.start, 1, 64);
-                r.end = lane < 63 ? nx : m.exit63;
-                r.kind = T_EXIT; r.reason = 0;
-                if ((uint32_t)lane == ft) { r.end = m.end_ft; r.kind = m.kind_ft; r.reason = m.reason_ft; }
+                rec_fetch(pool, rec, lane, pm, pst, pcn);
+                round_lane_end(m, r.start, lane, r.end, r.kind, r.reason);
                 g = make_geo(in, m.rs, m.rs + 1, m.pw);      // the count pass's staging geometry
                 stage_round(in, g, stg, lane);
             } else {
@@ -2678,15 +2261,12 @@ ndfl_inflate_emit_wave_kernel(const uint32_t* w, uint64_t nwords, uint64_t nbits
             uint32_t lastb = 0;             // the last output byte, when it is final (lastok)
             bool lastok = false;
             bool active = live;
-#if NDFL_BITBUF
             Bb bb;
             const uint32_t lim = min(end, nb - min(nb, 48u));
             bool fast = active && pos < lim;           // (pos only grows: once false, it stays false)
             if (fast) bb_init(bb, v, pos);
-#endif
             while (active && pos < end) {
                 Tok tk;
-#if NDFL_BITBUF
                 if (fast) {
                     tok_bb<true>(bb, v, S.t, ed, tk, end);
                     pos = bb.pos;
@@ -2694,10 +2274,6 @@ ndfl_inflate_emit_wave_kernel(const uint32_t* w, uint64_t nwords, uint64_t nbits
                 } else {
                     tok<true>(v, pos, S.t, ed, end, nb, tk);
                 }
-#else
-                if (pos + 48 < end) tok<false>(v, pos, S.t, ed, end, nb, tk);
-                else tok<true>(v, pos, S.t, ed, end, nb, tk);
-#endif
                 if (tk.kind == K_LIT) {
                     wr_lit(wr, gout, tk.val, tk.n);
                     n += tk.n;
@@ -2785,11 +2361,11 @@ ndfl_inflate_emit_wave_kernel(const uint32_t* w, uint64_t nwords, uint64_t nbits
         o.next = 0xFFFFFFFFu; o.pad = 0;
         o.bnd_bit = bnd_bit; o.bnd_cnt = bnd_out - ch.out_off;
         res[ci] = o;
-        if (stats) atomicMax((unsigned long long*)(stats + 32) + 20, (unsigned long long)(wall_clock64() - t_chain));
+        if (stats) atomicMax((unsigned long long*)(stats + SW_CLOCK64) + 20, (unsigned long long)(wall_clock64() - t_chain));
     }
     }
     if (stats && lane == 0) {                   // wave occupancy of the pass: busy sum, first start, last end
-        unsigned long long* st64 = (unsigned long long*)(stats + 32);
+        unsigned long long* st64 = (unsigned long long*)(stats + SW_CLOCK64);
         const uint64_t t_end = wall_clock64();
         atomicAdd(&st64[16], t_end - t_begin);
         atomicMax(&st64[17], t_end);
@@ -2802,21 +2378,14 @@ ndfl_inflate_emit_wave_kernel(const uint32_t* w, uint64_t nwords, uint64_t nbits
 // record and every round its segment record is replayed from those records alone (no header parse,
 // no table build, no round decode), so the kernel holds the registers of the record replay only:
 // 128 VGPRs, 11.0 KB of LDS (tables + the staged round), 14 waves per CU where the full emit kernel
-// holds 12 (measured: emit 8.81 -> 8.41 ms).  NDFL_EMITF_STAGE=0 reads the input through L1/L2
-// instead of the LDS stage (4 waves per SIMD; measured slower, 10.3 ms).  A chain that needs anything else (a block without a table record, a round without a
+// holds 12 (measured: emit 8.81 -> 8.41 ms; reading the input through L1/L2 instead of the LDS stage,
+// 4 waves per SIMD: slower, 10.3 ms).  The primary tables sit in LDS, the extension areas are read
+// from the table record; blocks of mostly 8-bit literal codes take four literals a step where they
+// can.  A chain that needs anything else (a block without a table record, a round without a
 // segment record, a stored block that is invalid or runs past the input) is listed in `slow` for the
 // full kernel, which runs it from its start: the output this kernel wrote for the chain so far is
 // rewritten there identically (the same records give the same segments, deferral decisions, bytes,
 // back-references and pending bits).
-#ifndef NDFL_EMITF_STAGE
-#define NDFL_EMITF_STAGE 1
-#endif
-#ifndef NDFL_EMITF_GX
-#define NDFL_EMITF_GX 1         // primary tables in LDS, extension areas read from the table record
-#endif
-#ifndef NDFL_EMIT_JUMP
-#define NDFL_EMIT_JUMP 1        // blocks of mostly 8-bit literal codes: four literals a step where they can
-#endif
 #ifndef NDFL_EMITF_WAVES_PER_SIMD
 #define NDFL_EMITF_WAVES_PER_SIMD 4
 #endif
@@ -2826,17 +2395,11 @@ ndfl_inflate_emit_fast_kernel(const uint32_t* w, uint64_t nwords, uint64_t nbits
                               SegPool pool, const uint64_t* info, const uint32_t* eorder, uint32_t* slow,
                               uint32_t* nslow) {
     using namespace wv;
-#if NDFL_EMITF_GX
     __shared__ __attribute__((aligned(16))) uint32_t Tp[(1u << LB) + (1u << DB)];     // primary tables
     TabsG T;
     T.lit = Tp;
     T.dst = Tp + (1u << LB);
-#else
-    __shared__ __attribute__((aligned(16))) Tabs T;
-#endif
-#if NDFL_EMITF_STAGE
     __shared__ Stage stg;
-#endif
     const int lane = threadIdx.x;
     gu8* gout = (gu8*)out;
     if (info[LI_FLAGS]) return;                 // (the host steps in: nothing to emit)
@@ -2857,7 +2420,7 @@ ndfl_inflate_emit_fast_kernel(const uint32_t* w, uint64_t nwords, uint64_t nbits
     SegMeta pm = {};
     uint64_t pst = 0;
     uint32_t pcn = 0;
-    if (rec != NOREC) { pm = pool.meta[rec]; pst = pool.start[(uint64_t)rec * 64 + lane]; pcn = pool.cnt[(uint64_t)rec * 64 + lane]; }
+    rec_fetch(pool, rec, lane, pm, pst, pcn);
     uint64_t bnd_bit = cur, bnd_out = base;
     for (int blk = 0;; blk++) {
         if (blk > 0 && cur == ch.end_bit) { status = ST_BOUNDARY; endpos = cur; break; }
@@ -2881,26 +2444,22 @@ ndfl_inflate_emit_fast_kernel(const uint32_t* w, uint64_t nwords, uint64_t nbits
             if (hb & 1) { status = ST_FINAL; endpos = cur; break; }
             continue;
         }
-        const char* btr = (rec != NOREC && pm.pad < pool.nbt) ? pool.bt + (uint64_t)pm.pad * BT_BYTES : nullptr;
-        if (!btr || *(const uint64_t*)(btr + sizeof(Tabs)) != cur) { abort = true; break; }
+        const TabRec* btr = block_tables(pool, rec, pm, cur);
+        if (!btr) { abort = true; break; }
         __syncthreads();                        // the previous block's table reads are done
         {
-            const uint4* src = (const uint4*)btr;
-#if NDFL_EMITF_GX
+            static_assert(offsetof(Tabs, lit) == 0 && offsetof(Tabs, dst) == sizeof(Tp) - sizeof(btr->t.dst), "primary tables first");
+            const uint4* src = (const uint4*)&btr->t;
             uint4* dst = (uint4*)Tp;
             for (uint32_t q = (uint32_t)lane; q < sizeof(Tp) / 16; q += 64) dst[q] = src[q];
-            T.lx = (const uint32_t*)btr + offsetof(Tabs, lx) / 4;
-            T.dx = (const uint32_t*)btr + offsetof(Tabs, dx) / 4;
-#else
-            uint4* dst = (uint4*)&T;
-            for (uint32_t q = (uint32_t)lane; q < sizeof(Tabs) / 16; q += 64) dst[q] = src[q];
-#endif
+            const TabsG tv = tabs_view(btr);
+            T.lx = tv.lx;
+            T.dx = tv.dx;
         }
-        const uint64_t* h = (const uint64_t*)(btr + sizeof(Tabs));
-        const uint32_t* h32 = (const uint32_t*)(h + 2);
-        const bool bfinal = h32[0] != 0, ed = h32[2] != 0;
-        const bool ph8 = NDFL_EMIT_JUMP && h32[3] != 0;     // mostly 8-bit literal codes
-        const uint32_t esc4 = h32[3] > 1 ? h32[3] : 0u;     // escape-prefix literal block (phase_multi_esc)
+        const bool bfinal = btr->bfinal != 0, ed = btr->ed != 0;
+        const uint32_t tph = btr->phase;
+        const bool ph8 = tph != TP_NONE;                    // mostly 8-bit literal codes
+        const uint32_t esc4 = tph > TP_LIT8 ? tph : 0u;     // escape-prefix literal block (phase_multi_esc)
         __syncthreads();
         bool block_done = false, chain_done = false;
         while (!block_done) {
@@ -2910,24 +2469,17 @@ ndfl_inflate_emit_fast_kernel(const uint32_t* w, uint64_t nwords, uint64_t nbits
             const uint64_t rstart = pst;
             const uint32_t rcnt = pcn;
             rec = m.next;
-            if (rec != NOREC) { pm = pool.meta[rec]; pst = pool.start[(uint64_t)rec * 64 + lane]; pcn = pool.cnt[(uint64_t)rec * 64 + lane]; }
-            const uint64_t nx = __shfl_down((unsigned long long)rstart, 1, 64);
-            uint64_t rend = lane < 63 ? nx : m.exit63;
-            uint32_t kind = T_EXIT, rsn = 0;
-            if ((uint32_t)lane == ft) { rend = m.end_ft; kind = m.kind_ft; rsn = m.reason_ft; }
+            rec_fetch(pool, rec, lane, pm, pst, pcn);
+            uint64_t rend;
+            uint32_t kind, rsn;
+            round_lane_end(m, rstart, lane, rend, kind, rsn);
             const Geo g = make_geo(in, m.rs, m.rs + 1, m.pw);      // the count pass's geometry
             const bool live = (uint32_t)lane <= ft;
             const uint64_t mycnt = live ? rcnt : 0ull;
             const uint64_t pre = wave_excl_u64(mycnt, lane);
             const uint64_t rsum = wave_sum_u64(mycnt);
-#if NDFL_EMITF_STAGE
             stage_round(in, g, stg, lane);
             const Lv v = make_lv(stg, g, lane);
-#else
-            Gv v;
-            v.rw = (uint32_t)lane * g.pw;
-            v.q = w + (g.base >> 5) + v.rw;
-#endif
             const uint32_t nb = g.nb;
             uint32_t pos = (uint32_t)(rstart - g.base);
             uint32_t end = (uint32_t)(rend - g.base);

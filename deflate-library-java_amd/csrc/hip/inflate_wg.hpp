@@ -80,15 +80,15 @@ __device__ __forceinline__ Geo make_geo_w(const In& in, uint64_t rs, uint64_t E)
     g.r0 = (uint32_t)(rs - g.base);
     g.re = (uint32_t)(E - g.base);
     const uint32_t span = g.re - g.r0;
-    g.pw = max((uint32_t)NDFL_PW_MIN, ((span + 64 * W - 1) / (64 * W) + 31) / 32);
+    g.pw = seg_pw(span, 64 * W);
     g.nb = (uint32_t)min(in.nbits - min(in.nbits, g.base), (uint64_t)0xFFFFFFFFu);
     return g;
 }
 template <int W>
 __device__ __forceinline__ void lane_seg_w(const Geo& g, uint32_t L, uint32_t& s, uint32_t& e) {
     const uint32_t per = g.pw * 32;
-    s = min(g.r0 + L * per, g.re);
-    e = L == 64 * W - 1 ? g.re : min(g.r0 + (L + 1) * per, g.re);
+    s = seg_start(g.r0, per, g.re, L);
+    e = seg_end(g.r0, per, g.re, L, 64 * W - 1);
 }
 // one wave stages its 64 lanes' regions (virtual lanes L = 64 * wave + lane)
 __device__ __forceinline__ void stage_wave(const In& in, const Geo& g, Stage& st, uint32_t L) {
@@ -99,7 +99,7 @@ __device__ __forceinline__ void stage_wave(const In& in, const Geo& g, Stage& st
 #pragma unroll 4
     for (uint32_t i = 0; i < SW; i++)
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(in.w + min(w0 + i, wmax)),
-                                         (__attribute__((address_space(3))) void*)&st.w[i * 64], 4, 0, NDFL_STAGE_CPOL);
+                                         (__attribute__((address_space(3))) void*)&st.w[i * 64], 4, 0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     wsync();
     (void)lane;
@@ -419,7 +419,7 @@ ndfl_inflate_count_wg_kernel(const uint32_t* w, uint64_t nwords, uint64_t nbits,
             }
             phased = n8 >= 192;
         }
-        const uint32_t esc4 = (phased && NDFL_PHASE_ESC) ? flat8_mask(S.t, lane) : 0u;
+        const uint32_t esc4 = phased ? flat8_mask(S.t, lane) : 0u;
         uint32_t brec = NOREC;
         if (recording && pool.nbt) {
             if (tid == 0) {
@@ -432,15 +432,15 @@ ndfl_inflate_count_wg_kernel(const uint32_t* w, uint64_t nwords, uint64_t nbits,
             __syncthreads();
             brec = X.b32[3];
             if (brec < pool.nbt) {
-                uint4* dst = (uint4*)(pool.bt + (uint64_t)brec * BT_BYTES);
+                // (by hand, not write_table_record: with it the 8-wave kernel spills one more register)
+                TabRec* tr = pool.bt + brec;
+                uint4* dst = (uint4*)&tr->t;
                 const uint4* src = (const uint4*)&S.t;
                 for (uint32_t q = (uint32_t)tid; q < sizeof(Tabs) / 16; q += NL) dst[q] = src[q];
                 if (tid == 0) {
-                    uint64_t* h = (uint64_t*)(pool.bt + (uint64_t)brec * BT_BYTES + sizeof(Tabs));
-                    h[0] = cur; h[1] = d0;
-                    uint32_t* h32 = (uint32_t*)(h + 2);
-                    h32[0] = S.h_bfinal; h32[1] = S.h_btype; h32[2] = ed ? 1u : 0u;
-                    h32[3] = phased ? (esc4 ? esc4 : 1u) : 0u;
+                    tr->hdr_bit = cur; tr->data_bit = d0;
+                    tr->bfinal = S.h_bfinal; tr->btype = S.h_btype; tr->ed = ed ? 1u : 0u;
+                    tr->phase = tab_phase(phased, esc4);
                 }
             } else {
                 brec = NOREC;
@@ -491,20 +491,11 @@ ndfl_inflate_count_wg_kernel(const uint32_t* w, uint64_t nwords, uint64_t nbits,
                         const uint64_t x63 = __shfl((unsigned long long)r.end, 63, 64);
                         uint32_t s0, e0;
                         lane_seg_w<W>(g, 64u * (uint32_t)wave, s0, e0);
-                        if (lane == 0) {
-                            SegMeta m;
-                            m.ft = wft; m.kind_ft = fk; m.reason_ft = fr;
-                            m.next = (uint32_t)wave + 1 < nlive ? idx + 1 : NOREC;
-                            m.end_ft = fe; m.exit63 = x63; m.pw = g.pw;
-                            m.pad = wave == 0 ? brec : NOREC;
-                            m.rs = g.base + s0;
-                            pool.meta[idx] = m;
-                        }
+                        if (lane == 0)
+                            write_round_meta(pool.meta + idx, wft, fk, fr, (uint32_t)wave + 1 < nlive ? idx + 1 : NOREC, fe,
+                                             x63, g.pw, wave == 0 ? brec : NOREC, g.base + s0);
                     }
-                    if (tid == 0) {
-                        if (prev_rec == NOREC) pool.head[slot_base + c] = idx0;
-                        else pool.meta[prev_rec].next = idx0;
-                    }
+                    if (tid == 0) link_round(pool, slot_base + c, prev_rec, idx0);
                     prev_rec = idx0 + nlive - 1;
                     brec = NOREC;
                 } else {
@@ -539,7 +530,7 @@ ndfl_inflate_count_wg_kernel(const uint32_t* w, uint64_t nwords, uint64_t nbits,
         o.pad = 0;
         o.bnd_bit = 0; o.bnd_cnt = 0;
         res[c] = o;
-        if (stats) { atomicAdd(&stats[0], nslow); atomicAdd(&stats[1], nfix); atomicAdd(&stats[2], nround); }
+        if (stats) { atomicAdd(&stats[SW_NSLOW], nslow); atomicAdd(&stats[SW_NFIX], nfix); atomicAdd(&stats[SW_NROUND], nround); }
     }
     }
 }
