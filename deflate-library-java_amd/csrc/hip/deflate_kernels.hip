@@ -122,7 +122,9 @@ constexpr int HREC = 320;                 // u32 per chunk histogram record
 constexpr int CREC_LIT = 0;               // u32[288] rev(code) | len << 16
 constexpr int CREC_DIST = 288;            // u32[32]
 constexpr int CREC_HDR = 320;             // u32[HDRW] header bits from local bit 0 (bfinal .. code-length symbols)
-constexpr int HDRW = 80;                  // >= 3 + 14 + 57 + 316 * 7 = 2286 bits (every code-length entry costs <= 7 bits)
+constexpr int HDRW = 80;                  // >= 3 + 14 + 57 + 316 * 7 = 2286 bits: <= 7 bits per code length (a plain entry
+                                          // is one <= 7-bit code; symbols 16/17/18 cost up to 9/10/14 bits but stand for
+                                          // >= 3/3/11 lengths)
 constexpr int CREC_META = CREC_HDR + HDRW;  // [0] hdrBits
 constexpr int CREC = CREC_META + 16;
 enum { MODE_FUSED = 0, MODE_HIST = 1, MODE_EMIT = 2 };
@@ -180,7 +182,10 @@ __device__ void pm_lengths(const uint32_t* hist, int n, int L, uint8_t* lens, ch
         lens[t] = 0;
     }
     __syncthreads();
-    const bool work = active && nl >= 2;   // otherwise all zero lengths (callers never need this for litlen/dist)
+    // otherwise all zero lengths.  No caller gets here for litlen/dist: an empty block counts a dummy
+    // literal next to the end-of-block symbol, a single distance code gets its dummy neighbour, and an
+    // unused distance alphabet is not `active` (tests/test_gpu_code_edges.py, class dist_fixups)
+    const bool work = active && nl >= 2;
     uint32_t np = 0;
     uint32_t* pf = pfA;
     uint32_t* pfn = pfB;

@@ -3,13 +3,17 @@
   (1) N-version agreement with tests/pyref_deflate.py (independent restatement, different algorithms),
   (2) the hand-derived known-answer tests of SURVEY.md App. A.8,
   (3) round-trip validity through Python zlib and through the oracle's own decoder,
-  (4) equivalence of the exhaustive distance loop and the exact-prefix chain walk (FULL_*).
+  (4) equivalence of the exhaustive distance loop and the exact-prefix chain walk (FULL_*),
+  (5) the same on the inputs of tests/adversarial_hist.py, which make the 15-bit and 7-bit length
+      limits bind and reach the header's edge cases, each with its engagement condition asserted
+      on the oracle's own stream (so a generator that stops reaching its edge fails here).
 """
 import random
 import zlib
 
 import pytest
 
+import adversarial_hist as A
 import oracle_lib as O
 import pyref_deflate as P
 
@@ -184,3 +188,93 @@ def test_strategy_ref_pinned_by_oracle():
         O.deflate_multi(data, [(1, 3, 258, 1, 1), "UNCOMPRESSED"])
     assert R.stream(data, R.Split(R.UncLeaf(), 1000)) == O.deflate_binsplit(data, "UNCOMPRESSED", 1000)
     assert R.stream(data, R.Split(R.LzLeaf("RLE_DYNAMIC"), 2000)) == O.deflate_binsplit(data, (1, 3, 258, 1, 1), 2000)
+
+
+# ---- code construction at the length limits and header edges (tests/adversarial_hist.py) ----
+
+def _oracle_streams(case):
+    """(label, oracle stream, pyref stream or None) per way `case` is encoded."""
+    mode, arg, chunk_len, hist = case.encode_args
+    if mode == "preset":
+        return [(st, O.deflate(case.data, st, chunk_len, hist), P.deflate(case.data, st, chunk_len, hist)) for st in arg]
+    comp = O.deflate_lz(case.data, *arg, chunk_len, hist)
+    slow = arg[4] > 1 and len(case.data) > 20000       # pyref's distance loop is quadratic
+    return [(arg, comp, None if slow else P.deflate(case.data, chunk_len=chunk_len, hist_limit=hist, params=arg))]
+
+
+BRUTE = {"fib_to29", "lz_all_codes"}        # the exhaustive loop takes seconds at these sizes: two cases
+
+
+@pytest.mark.parametrize("cls", A.CLASSES)
+def test_adversarial_cases(cls):
+    """Every generator case: oracle == pyref (or, for the large-distance LZ cases, the planned parse,
+    the exhaustive distance loop on two of them, and package-merge of the walked histograms), zlib
+    round trip, header lengths == pyref's package_merge of the walked histograms at 15 / 15 / 7, and
+    the class's engagement condition on the first way the case is encoded."""
+    for case in A.cases(cls):
+        for k, (label, comp, ref) in enumerate(_oracle_streams(case)):
+            where = (cls, case.name, label)
+            assert zlib.decompress(comp, -15) == case.data, where
+            if ref is not None:
+                assert comp == ref, (where, A.explain(ref, comp))
+            blocks = A.walk_blocks(comp)
+            assert (blocks[-1]["end_bit"] + 7) // 8 == len(comp), where
+            for b in blocks:
+                assert (b["lit_lens"], b["dist_lens"], b["cl_lens"]) == A.expected_lengths(b), (where, b["bit"])
+            if case.plan is not None:
+                copies = [t for t in blocks[0]["tokens"] if not isinstance(t, int)]
+                assert len(blocks) == 1 and copies == [(4, d) for _, d in case.plan], where
+            if case.name in BRUTE:
+                mode, arg, chunk_len, hist = case.encode_args
+                assert O.deflate_lz(case.data, *arg, chunk_len, hist, brute=True) == comp, where
+            if k == 0:
+                assert A.engaged(case.kind, blocks), where
+
+
+def test_adversarial_case_counts():
+    """What the issue of these tests asks each class to hold."""
+    n = {cls: len(A.cases(cls)) for cls in A.CLASSES}
+    assert n["lit_limit"] >= 11 and n["cl_limit"] >= 3 and n["dist_limit"] == 3 and n["dist_fixups"] >= 5
+    assert max(len(c.data) for cls in A.CLASSES for c in A.cases(cls)) <= 65536
+    assert all(len(c) == 512 for c in A.cl_runs_sweep_chunks())
+    assert len(A.cases("lit_limit")[6].data) == 65535
+    assert [len(c.data) for c in A.cases("all_symbols")][0] == 33920
+
+
+def test_adversarial_hclen_reached():
+    """The HCLEN values (as counts) the cases reach; 4 cannot occur (adversarial_hist docstring)."""
+    seen = set()
+    for cls in A.CLASSES:
+        for case in A.cases(cls):
+            for _, comp, _ in _oracle_streams(case)[:1]:
+                seen |= {b["hclen"] for b in A.walk_blocks(comp) if b["btype"] == 2}
+    assert 4 not in seen
+    assert seen >= A.HCLEN_REACHED, sorted(seen)
+
+
+def test_tie_pairs_counter():
+    assert A.tie_pairs([1, 1, 2, 2, 2, 2], 15) == 1          # the package 1+1 meets the leaves of 2
+    assert A.tie_pairs([1, 2, 4, 8, 16], 15) == 0            # packages 3, 7, 15: no leaf has those
+    assert A.tie_pairs([8] * 16, 15) == 0                    # packages are 16, 32, ...
+    assert A.tie_pairs([1] * 16 + [2] * 16, 15) == 8         # eight packages of 2 meet sixteen leaves of 2
+
+
+def test_walk_blocks_replays_input():
+    """walk_blocks pinned: its tokens decode back to the input, on a 15-bit literal code, a 15-bit
+    distance code, the 101-block sweep, and a stream of stored, static and dynamic blocks."""
+    lit = A.cases("lit_limit")[6]
+    dist = A.cases("dist_limit")[0]
+    sweep = A.cases("cl_runs")[0]
+    mixed = sweep.data[:3000] + random.Random(9).randbytes(3000)
+    for data, comp in [(lit.data, O.deflate(lit.data, "LITERAL_DYNAMIC")),
+                       (dist.data, O.deflate_lz(dist.data, *dist.encode_args[1])),
+                       (sweep.data, O.deflate(sweep.data, "RLE_DYNAMIC", 512, 0)),
+                       (mixed, O.deflate_mixed(mixed, ["RLE_DYNAMIC", "UNCOMPRESSED", "FULL_STATIC"], 1000))]:
+        blocks = A.walk_blocks(comp)
+        assert A.replay(blocks) == data
+        assert [b["bit"] for b in blocks[1:]] == [b["end_bit"] for b in blocks[:-1]]
+        assert O.inflate(comp)[2] == blocks[-1]["end_bit"]
+    assert "streams equal" == A.explain(comp, comp)
+    bad = bytearray(O.deflate(lit.data, "LITERAL_DYNAMIC"))
+    bad[40] ^= 0x10
+    assert "block 0" in A.explain(O.deflate(lit.data, "LITERAL_DYNAMIC"), bytes(bad))
