@@ -10,7 +10,8 @@
 //      histograms;
 //   4. length-limited package-merge (exact reference tie order: packages before leaves on equal
 //      frequency, D/comp/Lz77Huffman.java:319-333) runs as parallel merge-path levels + a prefix
-//      backtrack; canonical codes are built from per-length bitmasks;
+//      backtrack; canonical codes are built from per-length bitmasks (huffman_build.hpp, shared with
+//      the split pipeline's codes kernel and the LZ77 encoder);
 //   5. each lane's token bits are block-scanned; the chunk's global bit offset comes from a
 //      decoupled look-back over per-chunk status words (chunk ids from an atomic ticket, so a
 //      workgroup only ever waits on workgroups that already started);
@@ -18,7 +19,8 @@
 //      with coalesced stores; the two boundary words of each chunk go to an edge list merged by
 //      ndfl_edge_fixup.
 // D/ = /root/reference/src/io/nayuki/deflate/
-#include "ndfl_common.hpp"
+#pragma once
+#include "huffman_build.hpp"
 
 namespace {
 
@@ -26,62 +28,22 @@ constexpr int DT = 1024;                  // threads per workgroup
 constexpr int NW = DT / 64;               // waves per workgroup
 constexpr int MAX_CHUNK = 65536;
 constexpr int OUTW = 18600;               // LDS bit-buffer words (>= 594,362 bits)
+static_assert(sizeof(HuffScr) <= OUTW * 4, "the code-construction scratch is laid over the bit buffer");
 
 constexpr uint64_t ST_AGG = 1ull << 62;
 constexpr uint64_t ST_PRE = 2ull << 62;
 constexpr uint64_t ST_VAL = (1ull << 62) - 1;
 
-// ---- LDS layout (bytes) -------------------------------------------------------------------
-// [0, OUTW*4)          bit buffer; during code construction it is overlaid by scratch below
-// then persistent small arrays.
-constexpr int SCR_HLIT = 0;                         // u32[288] literal/length histogram
-constexpr int SCR_HDIST = SCR_HLIT + 288 * 4;       // u32[32]
-constexpr int SCR_LAST = SCR_HDIST + 32 * 4;        // u8[1024] last byte of each lane
-constexpr int SCR_KEY = SCR_LAST + 1024;            // u32[288]
-constexpr int SCR_LF = SCR_KEY + 288 * 4;           // u32[288] sorted leaf freq
-constexpr int SCR_LS = SCR_LF + 288 * 4;            // u32[288] sorted leaf symbol
-constexpr int SCR_PFA = SCR_LS + 288 * 4;           // u32[304] packages
-constexpr int SCR_PFB = SCR_PFA + 304 * 4;          // u32[304]
-constexpr int SCR_MF = SCR_PFB + 304 * 4;           // u32[608] merged list
-constexpr int SCR_MPK = SCR_MF + 608 * 4;           // u32[15][20] is-package bits per level
-constexpr int SCR_LVL = SCR_MPK + 15 * 20 * 4;      // u32[16] leaves per level
-constexpr int SCR_LEN = SCR_LVL + 16 * 4;           // u8[320] code lengths (lit ++ dist)
-constexpr int SCR_CLLEN = SCR_LEN + 320;            // u8[32] code-length-code lengths
-constexpr int SCR_BLC = SCR_CLLEN + 32;             // u32[16] bl_count
-constexpr int SCR_NXC = SCR_BLC + 16 * 4;           // u32[16] next code
-constexpr int SCR_MASK = SCR_NXC + 16 * 4;          // u32[16][10] symbols-by-length bitmask
-constexpr int SCR_CLH = SCR_MASK + 16 * 10 * 4;     // u32[20] code-length histogram
-constexpr int SCR_MISC = SCR_CLH + 20 * 4;          // u32[16]
-constexpr int SCR_END = SCR_MISC + 16 * 4;
-static_assert(2 * SCR_END <= OUTW * 4, "scratch (two package-merge problems) must fit in the bit buffer");
-
+// Persistent LDS of a chunk workgroup, next to the bit buffer (two emit workgroups fit a CU).  Code
+// construction keeps its state in the scratch it lays over the bit buffer (huffman_build.hpp).
 struct Persist {
     uint32_t litCode[288];    // rev(code) | len << 16
     uint32_t distCode[32];
-    uint32_t clCode[20];
-    uint8_t clSym[320];
-    uint8_t clExtra[320];
-    uint16_t clOff[320];      // bit offset of each code-length symbol inside the header body
     uint64_t scan64[NW];
     uint32_t scan32[NW];
     uint32_t chunk;           // ticket
-    uint32_t nsym, ncl, hlit, hdist;
     uint32_t hdrBits;         // total header bits (incl. bfinal/btype)
-    uint32_t clBodyBits;
     uint64_t P;               // chunk global bit offset
-    uint32_t crcAcc[NW];
-};
-
-// The split passes (hist, emit) keep no code-construction state: a smaller block of persistent LDS,
-// so that two emit workgroups (bit buffer + this) fit a CU.
-struct PersistS {
-    uint32_t litCode[288];
-    uint32_t distCode[32];
-    uint64_t scan64[NW];
-    uint32_t scan32[NW];
-    uint32_t chunk;
-    uint32_t hdrBits;
-    uint64_t P;
     uint32_t crcAcc[NW];
 };
 
@@ -122,9 +84,6 @@ constexpr int HREC = 320;                 // u32 per chunk histogram record
 constexpr int CREC_LIT = 0;               // u32[288] rev(code) | len << 16
 constexpr int CREC_DIST = 288;            // u32[32]
 constexpr int CREC_HDR = 320;             // u32[HDRW] header bits from local bit 0 (bfinal .. code-length symbols)
-constexpr int HDRW = 80;                  // >= 3 + 14 + 57 + 316 * 7 = 2286 bits: <= 7 bits per code length (a plain entry
-                                          // is one <= 7-bit code; symbols 16/17/18 cost up to 9/10/14 bits but stand for
-                                          // >= 3/3/11 lengths)
 constexpr int CREC_META = CREC_HDR + HDRW;  // [0] hdrBits
 constexpr int CREC = CREC_META + 16;
 enum { MODE_FUSED = 0, MODE_HIST = 1, MODE_EMIT = 2 };
@@ -145,335 +104,6 @@ __device__ __forceinline__ void run_sym(uint32_t run, uint32_t& sym, uint32_t& n
         ne = 29 - __clz(r);
         sym = (ne << 2) + (r >> ne) + 257;
         ex = r & ((1u << ne) - 1);
-    }
-}
-
-// ---- Package-merge code lengths (D/comp/Lz77Huffman.java:309-335) ---------------------------
-// hist: n entries (LDS).  Writes lens[0..n) (LDS, u8).  Every thread of the block must call (the
-// barriers are shared); thread `t` of the calling group works on this problem when `active`, so two
-// independent problems (literal/length and distance codes) run side by side on disjoint thread
-// ranges with their own scratch `s`.
-__device__ void pm_lengths(const uint32_t* hist, int n, int L, uint8_t* lens, char* s, int t, bool active) {
-    uint32_t* key = (uint32_t*)(s + SCR_KEY);
-    uint32_t* lf = (uint32_t*)(s + SCR_LF);
-    uint32_t* ls = (uint32_t*)(s + SCR_LS);
-    uint32_t* pfA = (uint32_t*)(s + SCR_PFA);
-    uint32_t* pfB = (uint32_t*)(s + SCR_PFB);
-    uint32_t* mf = (uint32_t*)(s + SCR_MF);
-    uint32_t* mpk = (uint32_t*)(s + SCR_MPK);
-    uint32_t* lvl = (uint32_t*)(s + SCR_LVL);
-    if (active && t < n) {
-        uint32_t f = hist[t];
-        key[t] = f ? (f << 9 | (uint32_t)t) : 0xFFFFFFFFu;
-    }
-    if (active && t < 15 * 20) mpk[t] = 0;
-    __syncthreads();
-    // leaves sorted by (freq, symbol): rank by counting (n <= 288, broadcast LDS reads)
-    uint32_t nl = 0;
-    if (active) for (int j = 0; j < n; j++) nl += key[j] != 0xFFFFFFFFu;   // uniform per problem
-    if (active && t < n) {
-        uint32_t k = key[t];
-        if (k != 0xFFFFFFFFu) {
-            uint32_t r = 0;
-            for (int j = 0; j < n; j++) r += key[j] < k;
-            lf[r] = k >> 9;
-            ls[r] = (uint32_t)t;
-        }
-        lens[t] = 0;
-    }
-    __syncthreads();
-    // otherwise all zero lengths.  No caller gets here for litlen/dist: an empty block counts a dummy
-    // literal next to the end-of-block symbol, a single distance code gets its dummy neighbour, and an
-    // unused distance alphabet is not `active` (tests/test_gpu_code_edges.py, class dist_fixups)
-    const bool work = active && nl >= 2;
-    uint32_t np = 0;
-    uint32_t* pf = pfA;
-    uint32_t* pfn = pfB;
-    for (int it = 0; it < L; it++) {
-        const uint32_t m = np + nl;
-        if (work && (uint32_t)t < m) {
-            uint32_t f, pos;
-            bool isp = (uint32_t)t < np;
-            if (isp) {
-                f = pf[t];
-                // # leaves with freq < f
-                uint32_t lo = 0, hi = nl;
-                while (lo < hi) { uint32_t mid = (lo + hi) >> 1; if (lf[mid] < f) lo = mid + 1; else hi = mid; }
-                pos = (uint32_t)t + lo;
-            } else {
-                uint32_t r = (uint32_t)t - np;
-                f = lf[r];
-                // # packages with freq <= f
-                uint32_t lo = 0, hi = np;
-                while (lo < hi) { uint32_t mid = (lo + hi) >> 1; if (pf[mid] <= f) lo = mid + 1; else hi = mid; }
-                pos = r + lo;
-            }
-            mf[pos] = f;
-            if (isp) atomicOr(&mpk[it * 20 + (pos >> 5)], 1u << (pos & 31));
-        }
-        __syncthreads();
-        const uint32_t np2 = m >> 1;
-        if (work && (uint32_t)t < np2) pfn[t] = mf[2 * t] + mf[2 * t + 1];
-        __syncthreads();
-        np = np2;
-        uint32_t* tmp = pf; pf = pfn; pfn = tmp;
-    }
-    // backtrack: prefix of 2(nl-1) items at the last level; leaves in the prefix of each level.
-    if (work && t < 64) {
-        uint32_t m = 2 * (nl - 1);
-        for (int it = L - 1; it >= 0; it--) {
-            uint32_t cnt = 0;
-            if (t < 20) {
-                uint32_t w = mpk[it * 20 + t];
-                uint32_t lo = (uint32_t)t * 32;
-                if (lo + 32 <= m) cnt = __popc(w);
-                else if (lo < m) cnt = __popc(w & ((1u << (m - lo)) - 1));
-            }
-            cnt = wave_sum(cnt);
-            if (t == 0) lvl[it] = m - cnt;
-            m = 2 * cnt;
-        }
-    }
-    __syncthreads();
-    if (work && (uint32_t)t < nl) {
-        uint32_t c = 0;
-        for (int it = 0; it < L; it++) c += (uint32_t)t < lvl[it];
-        lens[ls[t]] = (uint8_t)c;
-    }
-    __syncthreads();
-}
-__device__ __forceinline__ void pm_lengths(const uint32_t* hist, int n, int L, uint8_t* lens, char* s) {
-    pm_lengths(hist, n, L, lens, s, (int)threadIdx.x, true);
-}
-
-// Canonical codes (D/comp/Lz77Huffman.java:368-391): rev(code) | len << 16.
-__device__ void canon_codes(const uint8_t* lens, int n, uint32_t* codes, char* s) {
-    uint32_t* blc = (uint32_t*)(s + SCR_BLC);
-    uint32_t* nxc = (uint32_t*)(s + SCR_NXC);
-    uint32_t* mask = (uint32_t*)(s + SCR_MASK);
-    const int tid = threadIdx.x;
-    if (tid < 16) blc[tid] = 0;
-    if (tid < 160) mask[tid] = 0;
-    __syncthreads();
-    if (tid < n) {
-        uint32_t l = lens[tid];
-        if (l) {
-            atomicAdd(&blc[l], 1u);
-            atomicOr(&mask[l * 10 + (tid >> 5)], 1u << (tid & 31));
-        }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t code = 0;
-        blc[0] = 0;
-        for (int b = 1; b < 16; b++) { code = (code + blc[b - 1]) << 1; nxc[b] = code; }
-    }
-    __syncthreads();
-    if (tid < n) {
-        uint32_t l = lens[tid];
-        uint32_t c = 0;
-        if (l) {
-            uint32_t rank = 0;
-            const int wi = tid >> 5;
-            for (int w = 0; w < wi; w++) rank += __popc(mask[l * 10 + w]);
-            rank += __popc(mask[l * 10 + wi] & ((1u << (tid & 31)) - 1));
-            uint32_t code = nxc[l] + rank;
-            c = (__brev(code) >> (32 - l)) | (l << 16);
-        }
-        codes[tid] = c;
-    }
-    __syncthreads();
-}
-
-// One lane's bits into the LDS bit buffer: a 32-bit accumulator (one shift-or per code); a code that
-// crosses the word boundary leaves its top bits as the next word's start (v >> (32 - nb_before),
-// 1..30 bits since n <= 30), and the word goes out with one LDS atomicOr.
-struct BitPut {
-    uint32_t lo;
-    uint32_t nb;
-    uint32_t wb;         // byte offset of the word being filled
-    char* buf;
-    __device__ __forceinline__ void init(uint32_t* b, uint32_t bitpos) {
-        buf = (char*)b; wb = (bitpos >> 5) * 4; nb = bitpos & 31; lo = 0;
-    }
-    __device__ __forceinline__ void put(uint32_t v, uint32_t n) {     // v < 2^n, n <= 30
-        const uint32_t nb0 = nb;
-        lo |= v << nb0;
-        nb = nb0 + n;
-        if (nb >= 32) {
-            atomicOr((uint32_t*)(buf + wb), lo);
-            wb += 4;
-            nb -= 32;
-            lo = v >> (32 - nb0);
-        }
-    }
-    __device__ __forceinline__ void flush() {
-        if (nb) atomicOr((uint32_t*)(buf + wb), lo);
-    }
-};
-
-constexpr uint32_t CL_EXTRA_BITS[3] = {2, 3, 7};
-
-// Code construction for one block, histograms already final (EOB counted).  Dynamic:
-// D/comp/Lz77Huffman.java:143-265 (trim, single-distance fix-up, package-merge lengths, canonical
-// codes, code-length RLE, code-length code, header sizes); static: the fixed codes of :394-410.
-// Leaves the code tables and header layout in `ps` and the reordered 3-bit code-length-code
-// lengths packed in misc[4..5] of the scratch.  All threads must call.
-__device__ __forceinline__ void build_block_codes(bool dynamic, char* scr, Persist& ps, uint64_t* dbg = nullptr) {
-    uint32_t* hlit = (uint32_t*)(scr + SCR_HLIT);
-    uint32_t* hdist = (uint32_t*)(scr + SCR_HDIST);
-    uint8_t* lens = (uint8_t*)(scr + SCR_LEN);
-    uint8_t* clLen = (uint8_t*)(scr + SCR_CLLEN);
-    uint32_t* clh = (uint32_t*)(scr + SCR_CLH);
-    uint32_t* misc = (uint32_t*)(scr + SCR_MISC);
-    const int tid = threadIdx.x;
-    if (!dynamic) {
-        // fixed codes (D/comp/Lz77Huffman.java:394-410)
-        if (tid < 288) {
-            uint32_t l = tid < 144 ? 8 : tid < 256 ? 9 : tid < 280 ? 7 : 8;
-            uint32_t code = tid < 144 ? 0x30 + tid : tid < 256 ? 0x190 + (tid - 144) : tid < 280 ? (tid - 256) : 0xC0 + (tid - 280);
-            ps.litCode[tid] = (__brev(code) >> (32 - l)) | (l << 16);
-        }
-        if (tid < 32) ps.distCode[tid] = (__brev((uint32_t)tid) >> 27) | (5u << 16);
-        if (tid == 0) { ps.hdrBits = 3; ps.nsym = 0; }
-        __syncthreads();
-    } else {
-        // trim litlen histogram, keep >= 257 (:148-151)
-        if (tid == 0) {
-            int ln = 286;
-            while (ln > 257 && hlit[ln - 1] == 0) ln--;
-            misc[0] = (uint32_t)ln;
-            // single used distance code -> dummy neighbour (:155-171)
-            int used = 0, first = -1;
-            for (int i = 0; i < 30; i++) if (hdist[i]) { used++; if (first < 0) first = i; }
-            if (used == 1) { if (first < 29) hdist[first + 1] = 1; else hdist[first - 1] = 1; }
-            int dn = 30;
-            while (dn > 1 && hdist[dn - 1] == 0) dn--;
-            misc[1] = (uint32_t)dn;
-            misc[2] = (dn == 1 && hdist[0] == 0) ? 1u : 0u;   // empty distance code
-        }
-        __syncthreads();
-        if (dbg && tid == 0) dbg[0] = wall_clock64();
-        const int ln = (int)misc[0], dn = (int)misc[1];
-        const bool emptyDist = misc[2] != 0;
-        // literal/length and distance lengths side by side: threads [0, 640) and [640, 1024)
-        if (emptyDist && tid == 0) lens[ln] = 0;
-        {
-            const bool isLit = tid < 640;
-            pm_lengths(isLit ? hlit : hdist, isLit ? ln : dn, 15, isLit ? lens : lens + ln,
-                       isLit ? scr : scr + SCR_END, isLit ? tid : tid - 640, isLit || !emptyDist);
-        }
-        if (dbg && tid == 0) dbg[1] = wall_clock64();
-        canon_codes(lens, ln, ps.litCode, scr);
-        canon_codes(lens + ln, dn, ps.distCode, scr);
-        if (dbg && tid == 0) dbg[2] = wall_clock64();
-        // code-length sequence RLE (:187-223) as maximal-run decomposition
-        const int nc = ln + dn;
-        uint32_t rstart = 0xFFFFFFFFu;
-        uint32_t v = 0;
-        if (tid < nc) {
-            v = lens[tid];
-            if (tid == 0 || lens[tid - 1] != v) rstart = (uint32_t)tid;
-        }
-        uint32_t rnext = min(block_excl_suffix_min<NW>(rstart, 0xFFFFFFFFu, ps.scan32), (uint32_t)nc);
-        uint32_t cnt = 0, Z = 0;
-        if (rstart != 0xFFFFFFFFu) {
-            Z = rnext - rstart;
-            if (v == 0) {
-                uint32_t q = Z / 138, r = Z % 138;
-                cnt = q + (r >= 3 ? 1 : r);
-            } else {
-                uint32_t rest = Z - 1, q = rest / 6, r = rest % 6;
-                cnt = 1 + q + (r >= 3 ? 1 : r);
-            }
-        }
-        uint32_t tot;
-        uint32_t off = block_excl_scan<uint32_t, NW>(cnt, ps.scan32, tot);
-        if (rstart != 0xFFFFFFFFu) {
-            uint32_t k = off;
-            if (v == 0) {
-                uint32_t L = Z;
-                while (L > 0) {
-                    uint32_t r = min(L, 138u);
-                    if (r < 3) { ps.clSym[k] = 0; ps.clExtra[k++] = 0; L -= 1; }
-                    else if (r < 11) { ps.clSym[k] = 17; ps.clExtra[k++] = (uint8_t)(r - 3); L -= r; }
-                    else { ps.clSym[k] = 18; ps.clExtra[k++] = (uint8_t)(r - 11); L -= r; }
-                }
-            } else {
-                ps.clSym[k] = (uint8_t)v; ps.clExtra[k++] = 0;
-                uint32_t L = Z - 1;
-                while (L >= 3) { uint32_t r = min(L, 6u); ps.clSym[k] = 16; ps.clExtra[k++] = (uint8_t)(r - 3); L -= r; }
-                while (L > 0) { ps.clSym[k] = (uint8_t)v; ps.clExtra[k++] = 0; L--; }
-            }
-        }
-        if (tid < 20) clh[tid] = 0;
-        __syncthreads();
-        if ((uint32_t)tid < tot) atomicAdd(&clh[ps.clSym[tid]], 1u);
-        __syncthreads();
-        if (dbg && tid == 0) dbg[3] = wall_clock64();
-        pm_lengths(clh, 19, 7, clLen, scr);
-        if (dbg && tid == 0) dbg[4] = wall_clock64();
-        canon_codes(clLen, 19, ps.clCode, scr);
-        if (dbg && tid == 0) dbg[5] = wall_clock64();
-        // per-symbol header bit offsets
-        uint32_t sb = 0;
-        if ((uint32_t)tid < tot) {
-            uint32_t sy = ps.clSym[tid];
-            sb = (ps.clCode[sy] >> 16) + (sy >= 16 ? CL_EXTRA_BITS[sy - 16] : 0);
-        }
-        uint32_t body;
-        uint32_t so = block_excl_scan<uint32_t, NW>(sb, ps.scan32, body);
-        if ((uint32_t)tid < tot) ps.clOff[tid] = (uint16_t)so;
-        if (tid == 0) {
-            const int order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-            int ncl = 19;
-            while (ncl > 4 && clLen[order[ncl - 1]] == 0) ncl--;    // (:230-234)
-            ps.ncl = (uint32_t)ncl;
-            ps.nsym = tot;
-            ps.hlit = (uint32_t)(ln - 257);
-            ps.hdist = (uint32_t)(dn - 1);
-            ps.clBodyBits = body;
-            ps.hdrBits = 3 + 14 + 3 * (uint32_t)ncl + body;
-            // stash reordered code-length-code lengths in misc[4..] (3 bits each, packed)
-            uint64_t packed = 0;
-            for (int i = 0; i < ncl; i++) packed |= (uint64_t)clLen[order[i]] << (3 * i);
-            misc[4] = (uint32_t)packed; misc[5] = (uint32_t)(packed >> 32);
-        }
-        __syncthreads();
-    }
-}
-
-// Block header (bfinal, btype, HLIT/HDIST/HCLEN, code-length-code lengths, code-length symbols:
-// D/comp/Lz77Huffman.java:134-135,236-258) and the end-of-block code after `tokTotal` token bits
-// (:285), ORed into the LDS bit buffer at local bit 0.  All threads must call (no barrier).
-__device__ __forceinline__ void emit_block_header(uint32_t* obuf, bool is_final, bool dynamic, const Persist& ps,
-                                                  uint32_t packedLo, uint32_t packedHi, uint32_t hdrBits,
-                                                  uint32_t tokTotal, uint32_t eobLen) {
-    const int tid = threadIdx.x;
-    const uint32_t bit0 = 0;
-    if (tid == 0) {
-        BitPut bp; bp.init(obuf, bit0);
-        bp.put(is_final ? 1u : 0u, 1);
-        bp.put(dynamic ? 2u : 1u, 2);
-        if (dynamic) {
-            bp.put(ps.hlit, 5);
-            bp.put(ps.hdist, 5);
-            bp.put(ps.ncl - 4, 4);
-            uint64_t packed = (uint64_t)packedLo | (uint64_t)packedHi << 32;
-            for (uint32_t i = 0; i < ps.ncl; i++) bp.put((uint32_t)(packed >> (3 * i)) & 7u, 3);
-        }
-        bp.flush();
-        // end-of-block symbol
-        BitPut be; be.init(obuf, bit0 + hdrBits + tokTotal);
-        be.put(ps.litCode[256] & 0xFFFF, eobLen);
-        be.flush();
-    }
-    if (dynamic && (uint32_t)tid < ps.nsym) {
-        const uint32_t sy = ps.clSym[tid];
-        BitPut bp; bp.init(obuf, bit0 + 17 + 3 * ps.ncl + ps.clOff[tid]);
-        bp.put(ps.clCode[sy] & 0xFFFF, ps.clCode[sy] >> 16);
-        if (sy >= 16) bp.put(ps.clExtra[tid], CL_EXTRA_BITS[sy - 16]);
-        bp.flush();
     }
 }
 
@@ -535,20 +165,28 @@ __device__ __forceinline__ void block_store(const uint32_t* obuf, uint64_t P, ui
     }
 }
 
+// The end-of-block code after the header and token bits (D/comp/Lz77Huffman.java:285).
+__device__ __forceinline__ void put_end_of_block(uint32_t* obuf, uint32_t bitpos, uint32_t code) {
+    BitPut be; be.init(obuf, bitpos);
+    be.put(code & 0xFFFF, code >> 16);
+    be.flush();
+}
+
 }  // namespace
 
 // One chunk, one 1024-thread workgroup.  MODE_FUSED does everything (chunk ids from a ticket,
 // look-back for the offset); the split pipeline runs it as MODE_HIST (load, CRC, histograms to
 // hist_out) and, after ndfl_deflate_codes_kernel and ndfl_deflate_offsets_kernel, MODE_EMIT (load,
-// code tables and header from the record, token bits at the precomputed offset).
-template <int MODE, class PS>
-__device__ __forceinline__ void deflate_chunk(const Args& a, uint32_t* obuf, PS& ps, uint32_t* hl4 = nullptr,
-                                              uint32_t* ctab = nullptr) {
-    char* scr = (char*)obuf;
-    uint32_t* hlit = (uint32_t*)(scr + SCR_HLIT);
-    uint32_t* hdist = (uint32_t*)(scr + SCR_HDIST);
-    uint8_t* lastb = (uint8_t*)(scr + SCR_LAST);
-    uint32_t* misc = (uint32_t*)(scr + SCR_MISC);
+// code tables and header from the record, token bits at the precomputed offset).  obuf is the bit
+// buffer, under MODE_FUSED first the code-construction scratch with the histograms, whose header
+// words are kept in hdrw[HDRW] while the buffer is zeroed; MODE_HIST passes only the 1024 last bytes.
+template <int MODE>
+__device__ __forceinline__ void deflate_chunk(const Args& a, uint32_t* obuf, Persist& ps, uint32_t* hdrw = nullptr,
+                                              uint32_t* hl4 = nullptr, uint32_t* ctab = nullptr) {
+    HuffScr* scr = (HuffScr*)obuf;
+    uint32_t* hlit = scr->hlit;
+    uint32_t* hdist = scr->hdist;
+    uint8_t* lastb = MODE == MODE_HIST ? (uint8_t*)obuf : scr->lastb;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63, wid = tid >> 6;
@@ -815,10 +453,10 @@ _Pragma("unroll")
 
     const uint64_t tp2 = wall_clock64();
     // ---- 4. code construction -------------------------------------------------------------------
-    uint32_t packedLo = 0, packedHi = 0;
     if constexpr (MODE == MODE_FUSED) {
-        build_block_codes(a.dynamic != 0, scr, ps, a.prof ? a.prof + (uint64_t)c * 16 + 8 : nullptr);
-        packedLo = misc[4]; packedHi = misc[5];
+        const uint32_t hb = build_block_codes<DT>(*scr, a.dynamic != 0, is_final, ps.litCode, ps.distCode);
+        if (tid < HDRW) hdrw[tid] = scr->hdr()[tid];
+        if (tid == 0) ps.hdrBits = hb;
     } else {
         const uint32_t* rec = a.codes + (uint64_t)c * CREC;
         if (tid < 288) ps.litCode[tid] = rec[CREC_LIT + tid];
@@ -879,11 +517,9 @@ _Pragma("unroll")
     // zero the bit buffer (scratch is dead from here on); one spare word for the final shift
     const uint32_t nwl = (uint32_t)((S + 31) >> 5) + 1;
     __syncthreads();
-    if (MODE == MODE_FUSED) {
-        for (uint32_t k = (uint32_t)tid; k < nwl; k += DT) obuf[k] = 0;
-    } else {
-        // the record's header words (zero past hdrBits) start the buffer
-        const uint32_t* hdr = a.codes + (uint64_t)c * CREC + CREC_HDR;
+    {
+        // the header words (zero past hdrBits), kept or from the record, start the buffer
+        const uint32_t* hdr = MODE == MODE_FUSED ? hdrw : a.codes + (uint64_t)c * CREC + CREC_HDR;
         const uint32_t hw = (hdrBits + 31) >> 5;
         for (uint32_t k = (uint32_t)tid; k < nwl; k += DT) obuf[k] = k < hw ? hdr[k] : 0u;
     }
@@ -891,13 +527,7 @@ _Pragma("unroll")
     const uint32_t bit0 = 0;
 
     // ---- 6. emit ------------------------------------------------------------------------------
-    if constexpr (MODE == MODE_FUSED) {
-        emit_block_header(obuf, is_final, a.dynamic != 0, ps, packedLo, packedHi, hdrBits, tokTotal, eobLen);
-    } else if (tid == 0) {
-        BitPut be; be.init(obuf, bit0 + hdrBits + tokTotal);
-        be.put(ps.litCode[256] & 0xFFFF, eobLen);
-        be.flush();
-    }
+    if (tid == 0) put_end_of_block(obuf, bit0 + hdrBits + tokTotal, ps.litCode[256]);
     {
         BitPut bp; bp.init(obuf, bit0 + hdrBits + myoff);
         const uint32_t d0c = d0 & 0xFFFF, d0l = d0 >> 16;
@@ -963,13 +593,13 @@ _Pragma("unroll")
     block_store(obuf, P, S, c, a.out, a.edge_w, a.edge_v);
     if (tid == 0) {
         if (a.prof) {
-            uint64_t* q = a.prof + (uint64_t)c * 16;
+            uint64_t* q = a.prof + (uint64_t)c * 8;
             q[0] = tp0; q[1] = tp1; q[2] = tp2; q[3] = tp3; q[4] = tp4; q[5] = tp5e; q[6] = tp5;
             q[7] = wall_clock64();
             (void)tp3a; (void)tp3b;
         }
     }
-    (void)is_final; (void)packedLo; (void)packedHi;
+    (void)is_final;
     asm volatile("" :: "v"(pfv));
 }
 
@@ -977,24 +607,25 @@ extern "C" __global__ void __launch_bounds__(DT, 8)
 ndfl_deflate_chunks_kernel(Args a) {
     __shared__ __attribute__((aligned(16))) uint32_t obuf[OUTW];
     __shared__ Persist ps;
-    deflate_chunk<MODE_FUSED>(a, obuf, ps);
+    __shared__ uint32_t hdrw[HDRW];
+    deflate_chunk<MODE_FUSED>(a, obuf, ps, hdrw);
 }
 
 // Split pipeline pass 1: CRC + histograms only (small LDS).
 extern "C" __global__ void __launch_bounds__(DT, 8)
 ndfl_deflate_hist_kernel(Args a) {
-    __shared__ __attribute__((aligned(16))) uint32_t obuf[(SCR_LAST + 1024) / 4];
+    __shared__ __attribute__((aligned(16))) uint32_t lastb[1024 / 4];
     __shared__ __attribute__((aligned(16))) uint32_t hl4[HCOPY * HSTR];
     __shared__ uint32_t ctab[1024];
-    __shared__ PersistS ps;
-    deflate_chunk<MODE_HIST>(a, obuf, ps, hl4, ctab);
+    __shared__ Persist ps;
+    deflate_chunk<MODE_HIST>(a, lastb, ps, nullptr, hl4, ctab);
 }
 
 // Split pipeline pass 4: token bits at the offset from ndfl_deflate_offsets_kernel.
 extern "C" __global__ void __launch_bounds__(DT, 8)
 ndfl_deflate_emit_kernel(Args a) {
     __shared__ __attribute__((aligned(16))) uint32_t obuf[OUTW];
-    __shared__ PersistS ps;
+    __shared__ Persist ps;
     deflate_chunk<MODE_EMIT>(a, obuf, ps);
 }
 

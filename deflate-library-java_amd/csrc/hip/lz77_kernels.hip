@@ -541,14 +541,14 @@ ndfl_lz_encode_kernel(LzEncArgs a) {
     __shared__ __attribute__((aligned(16))) uint32_t big[32768];   // steps (u16) -> scratch -> bit buffer
     __shared__ uint32_t tokm[2048];                                 // token starts, 1 bit per position
     __shared__ Persist ps;
+    __shared__ uint32_t hdrw[HDRW];                                 // the block header while `big` is zeroed
     __shared__ uint32_t wexit[16];                                  // the parse walk's true exit per wave
     static_assert(OUTW <= 32768, "bit buffer must fit the step array");
     uint32_t* obuf = big;
-    char* scr = (char*)big;
+    HuffScr& scr = *(HuffScr*)big;
     uint16_t* step = (uint16_t*)big;
-    uint32_t* hlit = (uint32_t*)(scr + SCR_HLIT);
-    uint32_t* hdist = (uint32_t*)(scr + SCR_HDIST);
-    uint32_t* misc = (uint32_t*)(scr + SCR_MISC);
+    uint32_t* hlit = scr.hlit;
+    uint32_t* hdist = scr.hdist;
     const int tid = threadIdx.x;
     const int lane = tid & 63, wid = tid >> 6;
 
@@ -715,8 +715,8 @@ ndfl_lz_encode_kernel(LzEncArgs a) {
 
     const uint64_t tq2 = a.stats ? wall_clock64() : 0;
     // ---- codes ---------------------------------------------------------------------------------
-    build_block_codes(a.dynamic != 0, scr, ps);
-    const uint32_t packedLo = misc[4], packedHi = misc[5];
+    const uint32_t hdrBits = build_block_codes<DT>(scr, a.dynamic != 0, is_final, ps.litCode, ps.distCode);
+    if (tid < HDRW) hdrw[tid] = scr.hdr()[tid];
     __syncthreads();
     const uint64_t tq3 = a.stats ? wall_clock64() : 0;
 
@@ -732,7 +732,6 @@ ndfl_lz_encode_kernel(LzEncArgs a) {
     uint32_t tokTotal;
     const uint32_t myoff = block_excl_scan<uint32_t, NW>(mybits, ps.scan32, tokTotal);
     const uint32_t eobLen = ps.litCode[256] >> 16;
-    const uint32_t hdrBits = ps.hdrBits;
     const uint64_t S = (uint64_t)hdrBits + tokTotal + eobLen;
     if (tid == 0) {
         if (c == 0) st_agent(&a.status[0], ST_PRE | (a.base_bit + S));
@@ -741,11 +740,11 @@ ndfl_lz_encode_kernel(LzEncArgs a) {
     }
     const uint32_t nwl = (uint32_t)((S + 31) >> 5) + 1;
     __syncthreads();
-    for (uint32_t k = (uint32_t)tid; k < nwl; k += DT) obuf[k] = 0;
+    for (uint32_t k = (uint32_t)tid; k < nwl; k += DT) obuf[k] = k < ((hdrBits + 31) >> 5) ? hdrw[k] : 0u;
     __syncthreads();
 
     // ---- emit ----------------------------------------------------------------------------------
-    emit_block_header(obuf, is_final, a.dynamic != 0, ps, packedLo, packedHi, hdrBits, tokTotal, eobLen);
+    if (tid == 0) put_end_of_block(obuf, hdrBits + tokTotal, ps.litCode[256]);
     {
         BitPut bp; bp.init(obuf, hdrBits + myoff);
         NDFL_FOR_TOKENS({

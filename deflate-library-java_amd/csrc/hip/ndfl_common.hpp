@@ -21,7 +21,8 @@ struct Knobs {
     bool no_alias = false;       // NDFL_NO_ALIAS: every stored-header alias counted
     uint32_t count_w = 0;        // NDFL_COUNT_W: waves per chain in the count pass (0: automatic)
     bool deflate_pf = true;      // NDFL_DEFLATE_PF=0: no L2 touch of the next chunk in the encoder
-    bool deflate_profile = false;  // NDFL_DEFLATE_PROFILE: per-phase encoder clocks (one-kernel encoder)
+    bool deflate_profile = false;  // NDFL_DEFLATE_PROFILE: per-phase encoder clocks (one-kernel encoder); code
+                                   //   construction is the one `codes` figure (huffman_build.hpp has no clocks)
     bool deflate_fused = false;  // NDFL_DEFLATE_FUSED: the one-kernel encoder instead of the split passes
     bool lz_stats = false;       // NDFL_LZ_STATS
     bool lz_chain = false;       // NDFL_LZ_SEARCH=chain: the round-3 hash-chain LZ77 search
@@ -198,6 +199,19 @@ __device__ inline uint32_t block_excl_suffix_min(uint32_t v, uint32_t ident, uin
     uint32_t r = (lane == 63) ? after : min(nxt, after);
     __syncthreads();
     return r;
+}
+
+// The same over one wave.
+__device__ __forceinline__ uint32_t wave_excl_suffix_min(uint32_t v, uint32_t ident) {
+    const int lane = threadIdx.x & 63;
+    uint32_t x = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t y = __shfl_down(x, o, 64);
+        if (lane + o < 64) x = min(x, y);
+    }
+    const uint32_t nxt = __shfl_down(x, 1, 64);
+    return lane == 63 ? ident : nxt;
 }
 
 // Agent-scope relaxed atomics on 64-bit status words (decoupled look-back).

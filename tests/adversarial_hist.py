@@ -1,8 +1,8 @@
 """Inputs that drive the encoder's per-block code construction to its limits, and a header walker.
 
-The GPU encoder builds every dynamic block's codes twice by hand (the wave-wide wpm_lengths / wcanon
-/ ndfl_deflate_codes_kernel of deflate_split.hip, and the 1024-thread pm_lengths / canon_codes /
-build_block_codes of deflate_kernels.hip).  Random bytes, short runs and Zipf text never make the
+The GPU encoder builds every dynamic block's codes with one builder (pm_lengths / canon_codes /
+build_block_codes of huffman_build.hpp), instantiated at 64 threads for the split pipeline's codes
+kernel and at 1024 threads for the one-kernel and the LZ77 encoders.  Random bytes, short runs and Zipf text never make the
 15-bit limit bind on the literal/length or distance alphabet, nor the 7-bit limit on the code-length
 alphabet; the generators below do, and also reach the single-distance-code fix-ups, HLIT = 286,
 HDIST = 30 and the code-length run lengths at which the run decomposition changes shape.

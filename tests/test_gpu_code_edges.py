@@ -2,11 +2,12 @@
 (15-bit literal/length and distance codes that need the limit, 7-bit code-length codes that need it,
 long package/leaf tie chains, the single-distance-code fix-ups, HLIT = 286, HDIST = 30, code-length
 runs around every length at which the run decomposition changes) through each encoder that builds
-codes, byte for byte against the CPU oracle:
+codes, byte for byte against the CPU oracle.  There is one builder (huffman_build.hpp), instantiated
+at 64 and at 1024 threads:
 
-    split   the default pipeline's wave-wide codes kernel (wpm_lengths / wcanon, deflate_split.hip)
+    split   the default pipeline's codes kernel: build_block_codes at 64 threads (deflate_split.hip)
     fused   NDFL_DEFLATE_FUSED=1: build_block_codes at 1024 threads (deflate_kernels.hip)
-    lz      build_block_codes inside the LZ77 kernel, literal and distance merges side by side
+    lz      build_block_codes at 1024 threads inside the LZ77 kernel (lz77_kernels.hip)
 
 and the decoder on the oracle's streams of the same inputs.  The engagement condition of every case
 is asserted on the oracle's stream by the CPU suite (test_oracle_deflate.test_adversarial_cases);

@@ -101,3 +101,33 @@ def test_record_kernels_do_not_grow(kernel):
     assert k["vgpr_spill_count"] <= spills, k
     assert k["vgpr_count"] <= vgprs, k
     assert k["group_segment_fixed_size"] <= lds, k
+
+
+# The encoder kernels around the one code builder (huffman_build.hpp), measured before it replaced the
+# wave-wide and the 1024-thread builders.  The split passes use no scratch and spill nothing; the
+# one-kernel encoder and the LZ77 encoder must not add to theirs (the LZ77 encoder's 192 B are no
+# spills: its argument block, which the parse walk's lambdas capture by reference, is copied to the
+# stack at entry; the same before and after, not the builder's).  Upper bounds: smaller is
+# welcome.  VGPRs of the two 1024-thread encoders are bounded by their launch bounds instead: 512 per
+# SIMD over the 4 waves a workgroup puts on it (LZ77), over the 8 waves asked for (one-kernel encoder).
+ENCODER_KERNEL_BOUNDS = {
+    # kernel: scratch B, vgpr spills, sgpr spills, vgprs, LDS B
+    "ndfl_lz_encode_kernel": (192, 0, 0, 128, 142272),
+    "ndfl_deflate_chunks_kernel": (36, 13, 68, 64, 77336),
+    "ndfl_deflate_codes_kernel": (0, 0, 0, 44, 8784),
+    "ndfl_deflate_hist_kernel": (0, 0, 0, 43, 18832),
+    "ndfl_deflate_emit_kernel": (0, 0, 0, 64, 75952),
+}
+
+
+@needs_tools
+@pytest.mark.parametrize("kernel", sorted(ENCODER_KERNEL_BOUNDS))
+def test_encoder_kernels_do_not_grow(kernel):
+    k = kernel_metadata()[kernel]
+    scratch, spills, sspills, vgprs, lds = ENCODER_KERNEL_BOUNDS[kernel]
+    print(kernel, k)
+    assert k["private_segment_fixed_size"] <= scratch, k
+    assert k["vgpr_spill_count"] <= spills, k
+    assert k["sgpr_spill_count"] <= sspills, k
+    assert k["vgpr_count"] <= vgprs, k
+    assert k["group_segment_fixed_size"] <= lds, k
