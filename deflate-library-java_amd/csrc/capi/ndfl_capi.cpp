@@ -6,6 +6,7 @@
 #include "../hip/lz77_kernels.hip"
 #include "../hip/strategy_kernels.hip"
 #include "../hip/inflate_kernels.hip"
+#include "../hip/inflate_batch.hip"
 
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -74,6 +75,7 @@ struct ndfl_ctx {
     uint64_t* cb_out = nullptr;     // internal: when set, encoders also write per-chunk block bits here
     uint32_t parent_len = 0;        // internal: history rule of BinarySplit sub-blocks (0: chunk_len)
     InflateScratch inf;
+    BatchScratch batch;             // ndfl_inflate_batch: items / results / host-output staging
     uint32_t* h_pinned = nullptr;   // small pinned area for results
     Knobs knobs;                    // switches read once at ndfl_ctx_create (ndfl_common.hpp)
     int err_sym = -1;               // the last decode's reserved symbol (ndfl_ctx_error_symbol), or -1
@@ -171,6 +173,7 @@ int ndfl_ctx_destroy(ndfl_ctx* c) {
     for (DevBuf* b : bufs) b->release();
     for (int k = 0; k < 16; k++) { c->d_mstreams[k].release(); c->d_mbits[k].release(); }
     c->inf.release();
+    c->batch.release();
     if (c->h_pinned) hipHostFree(c->h_pinned);
     if (c->ev0) hipEventDestroy(c->ev0);
     if (c->ev1) hipEventDestroy(c->ev1);
@@ -1001,6 +1004,41 @@ int ndfl_inflate(ndfl_ctx* c, const uint8_t* in, uint64_t in_len, uint8_t* out, 
     HIPCHK(hipSetDevice(c->device));
     return public_reason(c, inflate_run(c->inf, ordered_stream(c), in, in_len, 0, inf::NONE, out, 0, out_cap, out_len,
                                         consumed_bits, flags, false, &c->last_ms));
+}
+
+int ndfl_inflate_batch(ndfl_ctx* c, const uint8_t* in, uint64_t in_size, uint8_t* out, uint64_t out_size,
+                       const ndfl_batch_item* items, ndfl_batch_result* results, uint32_t n, uint32_t flags) {
+    if (!c) return NDFL_E_ARG;
+    if (n == 0) return NDFL_OK;
+    if (!items || !results || (!in && in_size) || (!out && out_size)) return NDFL_E_ARG;
+    std::vector<std::pair<uint64_t, uint64_t>> regions;          // non-empty output regions [off, end)
+    regions.reserve(n);
+    for (uint32_t i = 0; i < n; i++) {
+        const ndfl_batch_item& it = items[i];
+        if (it.in_off > in_size || it.in_len > in_size - it.in_off) return NDFL_E_ARG;
+        if (it.out_off > out_size || it.out_cap > out_size - it.out_off) return NDFL_E_ARG;
+        if (it.out_cap) regions.emplace_back(it.out_off, it.out_off + it.out_cap);
+    }
+    std::sort(regions.begin(), regions.end());
+    for (size_t k = 1; k < regions.size(); k++)
+        if (regions[k].first < regions[k - 1].second) return NDFL_E_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    const int r = inflate_batch_run(c->inf, c->batch, ordered_stream(c), c->ev0, c->ev1, in, in_size, out, items,
+                                    results, n, flags, &c->last_ms);
+    if (r) return r == -4 ? NDFL_E_DEVICE : NDFL_E_INTERNAL;
+    for (uint32_t i = 0; i < n; i++) {                            // (public_reason, per stream)
+        ndfl_batch_result& q = results[i];
+        q.error_symbol = -1;
+        switch (q.status) {
+            case inf::R_RESERVED_LEN: q.error_symbol = 286; break;
+            case inf::R_RESERVED_LEN_HI: q.error_symbol = 287; q.status = inf::R_RESERVED_LEN; break;
+            case inf::R_RESERVED_DIST: q.error_symbol = 30; break;
+            case inf::R_RESERVED_DIST_HI: q.error_symbol = 31; q.status = inf::R_RESERVED_DIST; break;
+            case inf::R_INTERNAL: q.status = NDFL_E_INTERNAL; break;
+            default: break;
+        }
+    }
+    return NDFL_OK;
 }
 
 int ndfl_inflate_range(ndfl_ctx* c, const uint8_t* in, uint64_t in_len, uint64_t start_bit, uint64_t end_bit,

@@ -345,6 +345,56 @@ class Context:
         message (the symbol appended where D/decomp/Open.java appends it)."""
         return DataFormatException(Reason(code - 1), symbol=self.error_symbol())
 
+    def data_format_error_for(self, result):
+        """The DataFormatException of one stream of a batch: `result` is its (code, error_symbol, out_len,
+        consumed_bits) from inflate_batch_raw, code a Reason+1; the message names the stream's own
+        reserved symbol."""
+        return DataFormatException(Reason(result[0] - 1), symbol=result[1])
+
+    def inflate_batch_raw(self, in_addr, in_size, out_addr, out_size, items, flags):
+        """ndfl_inflate_batch: `items` is a sequence of (in_off, in_len, out_off, out_cap).  Returns one
+        (code, error_symbol, out_len, consumed_bits) per stream; code = 0 / Reason+1 / E_CAPACITY."""
+        L = load()
+        self._order()
+        n = len(items)
+        arr = (_lib.BatchItem * max(1, n))(*[_lib.BatchItem(*map(int, it)) for it in items])
+        res = (_lib.BatchResult * max(1, n))()
+        check(L.ndfl_inflate_batch(self._h, in_addr, in_size, out_addr, out_size, arr, res, n, flags),
+              "ndfl_inflate_batch")
+        return [(r.status, r.error_symbol, r.out_len, r.consumed_bits) for r in res[:n]]
+
+    def inflate_batch(self, streams, out_caps=None):
+        """Decode many independent raw DEFLATE streams (host bytes) in one call.  Returns one
+        (reason|None, bytes, consumed_bits) per stream.  With out_caps (one capacity per stream) a stream
+        that needs more raises NdflError(E_CAPACITY); without, every region is 4 * len + 65536 bytes and
+        only the streams that overflowed are run again, with the size they reported."""
+        streams = [bytes(s) for s in streams]
+        n = len(streams)
+        done = [None] * n
+        todo = list(range(n))
+        caps = [4 * len(s) + 65536 for s in streams] if out_caps is None else [int(c) for c in out_caps]
+        while todo:
+            packed = b"".join(streams[i] for i in todo)
+            src = ctypes.create_string_buffer(packed, max(1, len(packed)))
+            items, in_off, out_off = [], 0, 0
+            for i in todo:
+                items.append((in_off, len(streams[i]), out_off, caps[i]))
+                in_off += len(streams[i])
+                out_off += caps[i]
+            out = ctypes.create_string_buffer(max(1, out_off))
+            res = self.inflate_batch_raw(ctypes.addressof(src), len(packed), ctypes.addressof(out), out_off, items, 0)
+            again = []
+            for i, it, r in zip(todo, items, res):
+                code, _, olen, bits = r
+                if code == _lib.E_CAPACITY and out_caps is None:
+                    caps[i] = olen
+                    again.append(i)
+                    continue
+                check(code, "ndfl_inflate_batch")
+                done[i] = (None if code == 0 else Reason(code - 1), ctypes.string_at(ctypes.addressof(out) + it[2], min(olen, it[3])), bits)
+            todo = again
+        return done
+
     def inflate_range_raw(self, in_addr, in_len, start_bit, end_bit, out_addr, dict_len, out_cap, flags):
         """ndfl_inflate_range: decode bits [start_bit, end_bit) into out_addr + dict_len, with the
         dict_len bytes at out_addr as the window.  Returns (code, out_len, consumed_bits)."""

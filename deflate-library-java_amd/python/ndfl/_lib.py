@@ -39,7 +39,8 @@ EXPORTS = ["ndfl_abi_version", "ndfl_error_string", "ndfl_ctx_create", "ndfl_ctx
            "ndfl_deflate_bound",
            "ndfl_inflate", "ndfl_inflate_range", "ndfl_inflate_resolve", "ndfl_bits_shift", "ndfl_crc32", "ndfl_adler32",
            "ndfl_crc32_combine", "ndfl_decide", "ndfl_compress_to", "ndfl_decision_free", "ndfl_inflate_sync",
-           "ndfl_inflate_tail", "ndfl_inflate_headers", "ndfl_inflate_tail_map", "ndfl_ctx_error_symbol"]
+           "ndfl_inflate_tail", "ndfl_inflate_headers", "ndfl_inflate_tail_map", "ndfl_ctx_error_symbol",
+           "ndfl_inflate_batch"]
 
 KIND_LZ77, KIND_UNCOMPRESSED = 0, 1
 
@@ -58,6 +59,18 @@ class StrategyDesc(ctypes.Structure):
     """ndfl_strategy_desc (include/ndfl.h)."""
     _fields_ = [("kind", ctypes.c_int32), ("dynamic", ctypes.c_int32), ("min_run", ctypes.c_int32),
                 ("max_run", ctypes.c_int32), ("min_dist", ctypes.c_int32), ("max_dist", ctypes.c_int32)]
+
+
+class BatchItem(ctypes.Structure):
+    """ndfl_batch_item (include/ndfl.h)."""
+    _fields_ = [("in_off", ctypes.c_uint64), ("in_len", ctypes.c_uint64),
+                ("out_off", ctypes.c_uint64), ("out_cap", ctypes.c_uint64)]
+
+
+class BatchResult(ctypes.Structure):
+    """ndfl_batch_result (include/ndfl.h)."""
+    _fields_ = [("status", ctypes.c_int32), ("error_symbol", ctypes.c_int32),
+                ("out_len", ctypes.c_uint64), ("consumed_bits", ctypes.c_uint64)]
 
 
 _lib = None
@@ -92,6 +105,11 @@ def load():
     L.ndfl_deflate_bound.restype = u64
     L.ndfl_deflate_bound.argtypes = [u64, u32]
     L.ndfl_inflate.argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(u64), u32]
+    # (a library built before the batch entry point existed still loads -- scripts/bench_batch.py
+    # --mode loop measures its baseline on one; Context.inflate_batch* then fail on the missing symbol)
+    if hasattr(L, "ndfl_inflate_batch"):
+        L.ndfl_inflate_batch.argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(BatchItem),
+                                         ctypes.POINTER(BatchResult), u32, u32]
     L.ndfl_inflate_range.argtypes = [vp, vp, u64, u64, u64, vp, u64, u64, ctypes.POINTER(u64), ctypes.POINTER(u64),
                                      u32]
     L.ndfl_inflate_resolve.argtypes = [vp, ctypes.POINTER(u64)]

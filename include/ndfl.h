@@ -222,6 +222,53 @@ int ndfl_inflate(ndfl_ctx* ctx, const uint8_t* in, uint64_t in_len, uint8_t* out
                  uint64_t* out_len, uint64_t* consumed_bits, uint32_t flags);
 
 /*
+ * Decompress n independent raw DEFLATE streams in one call: one kernel launch and one host sync
+ * whatever n is (ndfl_inflate costs several launches and two syncs per stream).  Each stream is
+ * decoded as ndfl_inflate decodes it -- InflaterInputStream.read / Open.read run to the end of the
+ * stream, the reference's checks in the reference's order, trailing bytes after the final block
+ * ignored -- by one wave, serially: the call is for MANY SMALL streams (zip entries, PNG IDAT
+ * payloads, per-record zlib bodies).
+ * Crossover (measured on one MI355X, DESIGN.md §4 "Batched inflate"): a wave decodes about 4 MB/s
+ * of output on 4 KiB streams and 7.6 MB/s on 1 MiB streams, and up to 1,024 waves run at once;
+ * ndfl_inflate costs about 0.57 ms per call plus 4 ns per output byte up to 1 MiB.  So one stream
+ * alone is faster through ndfl_inflate above about 4.5 KiB of output, ten streams above about 47 KiB
+ * each, and from about 34 streams on the batch is never slower for streams up to 1 MiB (256 x 1 MiB:
+ * 136 ms in a batch, 1,201 ms in a loop).  Streams of hundreds of MiB, which ndfl_inflate decodes at
+ * tens of GB/s by working inside the stream, belong there whatever their number.
+ *   in/in_size, out/out_size   the two buffers all items point into; NDFL_IN_DEVICE, NDFL_OUT_DEVICE
+ *               and NDFL_IN_PADDED (for the whole `in`) exactly as for ndfl_inflate
+ *   items       host memory.  Stream i is in[in_off, in_off + in_len): its input ends there (it never
+ *               sees its neighbour's bytes), and its dictionary starts empty at its own out_off (a
+ *               distance that reaches before it is COPY_FROM_BEFORE_DICTIONARY_START whatever lies
+ *               there in `out`).  Input regions may overlap or repeat; output regions must not overlap.
+ *   results     host memory, one per stream.  Status precedence: a Reason wins -- out_len is then
+ *               the bytes decoded before the error, of which the first min(out_len, out_cap) are
+ *               stored; otherwise a stream that decodes to more than out_cap bytes has status
+ *               NDFL_E_CAPACITY and out_len = the bytes required (the decode goes on without storing
+ *               past out_cap, so a later Reason still wins); otherwise 0.  consumed_bits (status 0) is
+ *               relative to the stream's own first bit.  error_symbol is this stream's
+ *               ndfl_ctx_error_symbol value (ndfl_ctx_error_symbol itself is not changed by the call).
+ * No byte of `out` outside [out_off, out_off + min(out_len, out_cap)) of some stream is written,
+ * whatever the statuses.
+ * Returns 0 when the batch ran (per-stream outcomes are in `results` only; n == 0 returns 0 and
+ * touches nothing); NDFL_E_ARG for null pointers with n > 0, an item outside in_size / out_size, or
+ * overlapping output regions (nothing is decoded); NDFL_E_DEVICE on HIP errors.
+ * ndfl_ctx_last_kernel_ms reports the batch kernel's time.
+ */
+typedef struct {
+    uint64_t in_off, in_len;     /* stream i is in[in_off, in_off + in_len) */
+    uint64_t out_off, out_cap;   /* its output region is out[out_off, out_off + out_cap) */
+} ndfl_batch_item;
+typedef struct {
+    int32_t  status;             /* 0, Reason+1 (1..19), or NDFL_E_CAPACITY */
+    int32_t  error_symbol;       /* as ndfl_ctx_error_symbol for this stream, else -1 */
+    uint64_t out_len;            /* as ndfl_inflate; with NDFL_E_CAPACITY: bytes required */
+    uint64_t consumed_bits;      /* relative to the stream's own first bit */
+} ndfl_batch_result;
+int ndfl_inflate_batch(ndfl_ctx* ctx, const uint8_t* in, uint64_t in_size, uint8_t* out, uint64_t out_size,
+                       const ndfl_batch_item* items, ndfl_batch_result* results, uint32_t n, uint32_t flags);
+
+/*
  * Decompress the block-aligned bit range [start_bit, end_bit) of one raw DEFLATE stream: one GPU's
  * shard of a stream decoded across GPUs, or one batch of a stream read incrementally
  * (NDFL_IN_PARTIAL, end_bit UINT64_MAX: InflaterInputStream's bounded input buffer,
