@@ -1006,28 +1006,33 @@ int ndfl_inflate(ndfl_ctx* c, const uint8_t* in, uint64_t in_len, uint8_t* out, 
                                         consumed_bits, flags, false, &c->last_ms));
 }
 
-int ndfl_inflate_batch(ndfl_ctx* c, const uint8_t* in, uint64_t in_size, uint8_t* out, uint64_t out_size,
-                       const ndfl_batch_item* items, ndfl_batch_result* results, uint32_t n, uint32_t flags) {
-    if (!c) return NDFL_E_ARG;
-    if (n == 0) return NDFL_OK;
-    if (!items || !results || (!in && in_size) || (!out && out_size)) return NDFL_E_ARG;
+}  // extern "C"
+
+// The call-level rules of ndfl_inflate_batch and ndfl_inflate_members (n > 0): the pointers, every
+// item inside its buffers, no two non-empty output regions overlapping.
+template <class Item>
+static bool batch_regions_valid(const uint8_t* in, uint64_t in_size, const uint8_t* out, uint64_t out_size,
+                                const Item* items, const void* results, uint32_t n) {
+    if (!items || !results || (!in && in_size) || (!out && out_size)) return false;
     std::vector<std::pair<uint64_t, uint64_t>> regions;          // non-empty output regions [off, end)
     regions.reserve(n);
     for (uint32_t i = 0; i < n; i++) {
-        const ndfl_batch_item& it = items[i];
-        if (it.in_off > in_size || it.in_len > in_size - it.in_off) return NDFL_E_ARG;
-        if (it.out_off > out_size || it.out_cap > out_size - it.out_off) return NDFL_E_ARG;
+        const Item& it = items[i];
+        if (it.in_off > in_size || it.in_len > in_size - it.in_off) return false;
+        if (it.out_off > out_size || it.out_cap > out_size - it.out_off) return false;
         if (it.out_cap) regions.emplace_back(it.out_off, it.out_off + it.out_cap);
     }
     std::sort(regions.begin(), regions.end());
     for (size_t k = 1; k < regions.size(); k++)
-        if (regions[k].first < regions[k - 1].second) return NDFL_E_ARG;
-    HIPCHK(hipSetDevice(c->device));
-    const int r = inflate_batch_run(c->inf, c->batch, ordered_stream(c), c->ev0, c->ev1, in, in_size, out, items,
-                                    results, n, flags, &c->last_ms);
-    if (r) return r == -4 ? NDFL_E_DEVICE : NDFL_E_INTERNAL;
-    for (uint32_t i = 0; i < n; i++) {                            // (public_reason, per stream)
-        ndfl_batch_result& q = results[i];
+        if (regions[k].first < regions[k - 1].second) return false;
+    return true;
+}
+
+// public_reason per stream: the kernel's internal codes become the Reason and the stream's symbol.
+template <class Result>
+static void batch_public_reasons(Result* results, uint32_t n) {
+    for (uint32_t i = 0; i < n; i++) {
+        Result& q = results[i];
         q.error_symbol = -1;
         switch (q.status) {
             case inf::R_RESERVED_LEN: q.error_symbol = 286; break;
@@ -1038,6 +1043,35 @@ int ndfl_inflate_batch(ndfl_ctx* c, const uint8_t* in, uint64_t in_size, uint8_t
             default: break;
         }
     }
+}
+
+extern "C" {
+
+int ndfl_inflate_batch(ndfl_ctx* c, const uint8_t* in, uint64_t in_size, uint8_t* out, uint64_t out_size,
+                       const ndfl_batch_item* items, ndfl_batch_result* results, uint32_t n, uint32_t flags) {
+    if (!c) return NDFL_E_ARG;
+    if (n == 0) return NDFL_OK;
+    if (!batch_regions_valid(in, in_size, out, out_size, items, results, n)) return NDFL_E_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    const int r = inflate_batch_run<false>(c->inf, c->batch, ordered_stream(c), c->ev0, c->ev1, in, in_size, out, items,
+                                           results, n, flags, &c->last_ms);
+    if (r) return r == -4 ? NDFL_E_DEVICE : NDFL_E_INTERNAL;
+    batch_public_reasons(results, n);
+    return NDFL_OK;
+}
+
+int ndfl_inflate_members(ndfl_ctx* c, const uint8_t* in, uint64_t in_size, uint8_t* out, uint64_t out_size,
+                         const ndfl_member_item* items, ndfl_member_result* results, uint32_t n, uint32_t flags) {
+    if (!c) return NDFL_E_ARG;
+    if (n == 0) return NDFL_OK;
+    if (!batch_regions_valid(in, in_size, out, out_size, items, results, n)) return NDFL_E_ARG;
+    for (uint32_t i = 0; i < n; i++)
+        if (items[i].format > NDFL_FMT_GZIP || items[i].sum > NDFL_SUM_ADLER32) return NDFL_E_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    const int r = inflate_batch_run<true>(c->inf, c->batch, ordered_stream(c), c->ev0, c->ev1, in, in_size, out, items,
+                                          results, n, flags, &c->last_ms, c->d_tabs.as<uint32_t>() + 1024);
+    if (r) return r == -4 ? NDFL_E_DEVICE : NDFL_E_INTERNAL;
+    batch_public_reasons(results, n);
     return NDFL_OK;
 }
 

@@ -31,6 +31,12 @@
 // the parse_hdr / build_tables wrappers: build_tables_l is __noinline__ and parse_hdr is not forced
 // inline, and a real call's stack lives in scratch memory, which this kernel must not have (DESIGN.md
 // §7 item 9: wrong values when two scratch-using waves of one kernel share a SIMD).
+//
+// ndfl_inflate_members_kernel (ndfl_inflate_members) is the same stream loop -- one text,
+// inflate_batch_loop.inc, included in both kernels -- for zlib members, gzip members and raw streams
+// with a checksum: lane 0 parses the container header before the DEFLATE data and the trailer after
+// it, and flush_to, where every output byte passes once and in order, folds what it flushes into the
+// stream's CRC-32 or Adler-32 (fold_span).  The same constraints hold for it.
 #pragma once
 
 namespace bat {
@@ -82,13 +88,103 @@ struct Out {
     uint8_t* ring;         // LDS, RING bytes, 16-byte aligned
     uint64_t obeg, oend, o, fl;
     uint32_t npend;        // literals held in registers (lane k holds the k-th), not yet in the ring
+    static constexpr bool members = false;
+};
+// The same with the checksum state of ndfl_inflate_members_kernel: the ring helpers below are
+// templates over the two, and flush_to folds what it flushes into an OutM's checksum.
+struct OutM : Out {
+    uint32_t sum;          // NDFL_SUM_* of the stream's checksum
+    uint32_t ck;           // its running value: the raw CRC register, or Adler's (b << 16) | a; wave-uniform,
+                           //   but kept in a vector register throughout
+    const uint32_t* crc_x; // the context's x^(8k) table (crc_x[k], k < 64) and x^(8 * 64k) (crc_x[64 + k])
+    static constexpr bool members = true;
 };
 
-// Store ring bytes [fl, fend) that lie inside the region; the ring keeps them.
-__device__ __forceinline__ void flush_to(Out& q, uint64_t fend, int lane) {
+__device__ __forceinline__ uint32_t to_v(uint32_t x);
+
+// The checksum code keeps its wave-uniform values in VECTOR registers (every lane computes the same
+// value): it runs inside the token loop, whose scalar registers are all taken.
+//
+// a*b mod P as crc_multmodp, without its data-dependent exit: 32 steps on vector registers.
+__device__ __forceinline__ uint32_t crc_mul_v(uint32_t a, uint32_t b) {
+    uint32_t p = 0;
+#pragma nounroll
+    for (int k = 0; k < 32; k++) {
+        p ^= b & (0u - (a >> 31));
+        a <<= 1;
+        b = (b >> 1) ^ (NDFL_CRC_POLY & (0u - (b & 1u)));
+    }
+    return p;
+}
+
+// x^(8n) mod P for n < 65536 from the context's table: one product instead of crc_x8n's ~30.
+__device__ __forceinline__ uint32_t x8n_tab(const uint32_t* crc_x, uint32_t n) {
+    return crc_mul_v(crc_x[n & 63], crc_x[64 + (n >> 6)]);
+}
+
+// One byte into a raw CRC register (no table: the tables stay out of LDS, and a lookup in global
+// memory would put a load's latency on every byte).
+__device__ __forceinline__ uint32_t crc_byte(uint32_t c, uint32_t b) {
+    c ^= b;
+#pragma unroll
+    for (int k = 0; k < 8; k++) c = (c >> 1) ^ (NDFL_CRC_POLY & (0u - (c & 1u)));
+    return c;
+}
+
+// Fold the L (<= RING) ring bytes from output address a on into the stream's checksum.  The span is
+// cut into 64 pieces of p bytes that END at the span's end, lane k taking the k-th: the first lanes'
+// pieces begin before the span, where they read zeros -- which change neither a raw CRC that starts
+// at 0 nor a sum -- so every piece has the same length and lane k is followed by (63 - k) * p bytes.
+// p is odd, so the lanes' byte reads spread over the LDS banks.
+//   Adler-32: each lane's (s1, s2) of its piece, s2 relative to the piece's own start; the wave adds
+//   s1 * (bytes after the piece) to s2 and sums.  p <= 513, so s1 <= 130,815 and s2 <= 255 * 513 *
+//   514 / 2 < 2^26 (a 32 KiB span of 0xFF); both are reduced mod 65521 before the products, which
+//   then stay below 65,520 * 32,768 < 2^31, and the sums of 64 of them below 2^32.
+//   CRC-32: each lane's raw CRC of its piece; six rounds of c = c * x^(8 * p * 2^j) ^ (the lane 2^j
+//   further on) leave the span's raw CRC in lane 0; then run = run * x^(8L) ^ span.
+__device__ __forceinline__ void fold_span(OutM& q, uint64_t a, uint32_t L, int lane) {
+    const uint32_t sum = (uint32_t)__builtin_amdgcn_readfirstlane(q.sum);    // (parked in a vector register)
+    if (sum == NDFL_SUM_NONE) return;
+    const uint32_t p = ((L + 63) >> 6) | 1u;                                 // (scalar: the loop bound)
+    const uint32_t Lv = to_v(L), pv = to_v(p);
+    uint32_t at = to_v((uint32_t)a) + Lv - (64u - (uint32_t)lane) * pv;      // this lane's next byte ...
+    int32_t idx = (int32_t)(Lv - (64u - (uint32_t)lane) * pv);               // ... and its index in the span
+    if (sum == NDFL_SUM_ADLER32) {
+        uint32_t s1 = 0, s2 = 0;
+        for (uint32_t j = 0; j < p; j++, idx++, at++) {
+            s1 += idx >= 0 ? (uint32_t)q.ring[at & RMASK] : 0u;
+            s2 += s1;
+        }
+        s1 %= 65521u;
+        const uint32_t t = s2 % 65521u + (s1 * ((63u - (uint32_t)lane) * pv)) % 65521u;
+        const uint32_t S1 = wave_sum(s1), T = wave_sum(t);
+        const uint32_t A = q.ck & 0xFFFFu, B = q.ck >> 16;
+        const uint32_t nb = (B + (Lv * A) % 65521u + T) % 65521u, na = (A + S1) % 65521u;
+        q.ck = nb << 16 | na;
+    } else {
+        uint32_t c = 0;
+        for (uint32_t j = 0; j < p; j++, idx++, at++) c = crc_byte(c, idx >= 0 ? (uint32_t)q.ring[at & RMASK] : 0u);
+        uint32_t X = x8n_tab(q.crc_x, pv);
+#pragma nounroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t next = __shfl_down(c, o, 64);
+            c = crc_mul_v(X, c) ^ next;
+            X = crc_mul_v(X, X);
+        }
+        const uint32_t span = (uint32_t)__builtin_amdgcn_readfirstlane(c);
+        q.ck = crc_mul_v(x8n_tab(q.crc_x, Lv), q.ck) ^ span;
+    }
+}
+
+// Store ring bytes [fl, fend) that lie inside the region; the ring keeps them.  Every output byte
+// of a stream passes here exactly once and in order, so the members kernel (an OutM) folds the span
+// into the stream's checksum here -- before the clamp to the region: bytes past out_cap count.
+template <class O>
+__device__ __forceinline__ void flush_to(O& q, uint64_t fend, int lane) {
     if (fend <= q.fl) return;
     wsync();                                   // the ring writes of other lanes
     uint64_t a = q.fl;
+    if constexpr (O::members) fold_span(q, a, (uint32_t)(fend - a), lane);
     const uint64_t b = min(fend, q.oend);
     q.fl = fend;
     if (a >= b) return;
@@ -104,10 +200,12 @@ __device__ __forceinline__ void flush_to(Out& q, uint64_t fend, int lane) {
 }
 // Room for n more bytes (n <= RING - 16): ring slots are reused only once flushed.  A flush between
 // blocks ends on a 16-byte boundary, so only a region's two ends see byte stores.
-__device__ __forceinline__ void make_room(Out& q, uint32_t n, int lane) {
+template <class O>
+__device__ __forceinline__ void make_room(O& q, uint32_t n, int lane) {
     if (q.o + n - q.fl > RING) flush_to(q, q.o & ~15ull, lane);
 }
-__device__ __forceinline__ void flush_pending(Out& q, uint32_t pend, int lane) {
+template <class O>
+__device__ __forceinline__ void flush_pending(O& q, uint32_t pend, int lane) {
     if (!q.npend) return;
     make_room(q, q.npend, lane);
     if ((uint32_t)lane < q.npend) q.ring[(q.o + lane) & RMASK] = (uint8_t)pend;
@@ -115,7 +213,8 @@ __device__ __forceinline__ void flush_pending(Out& q, uint32_t pend, int lane) {
     q.npend = 0;
     wsync();
 }
-__device__ __forceinline__ void add_literal(Out& q, uint32_t& pend, uint32_t b, int lane) {
+template <class O>
+__device__ __forceinline__ void add_literal(O& q, uint32_t& pend, uint32_t b, int lane) {
     pend = (uint32_t)lane == q.npend ? b : pend;
     if (++q.npend == 64) flush_pending(q, pend, lane);
 }
@@ -124,7 +223,8 @@ __device__ __forceinline__ void add_literal(Out& q, uint32_t& pend, uint32_t b, 
 // earlier steps; with dist near 32768 a step's sources share slots only with its own or later
 // destinations, and each step reads before it writes).  Otherwise the source is a period of dist
 // bytes: byte k comes from byte k mod dist of the last dist bytes, which no step overwrites.
-__device__ __forceinline__ void copy_run(Out& q, uint32_t n, uint32_t dist, int lane) {
+template <class O>
+__device__ __forceinline__ void copy_run(O& q, uint32_t n, uint32_t dist, int lane) {
     make_room(q, n, lane);
     const uint64_t src = q.o - dist;
     if (dist >= 64 || dist >= n) {
@@ -167,156 +267,120 @@ __device__ __forceinline__ void unpark(Out& q, uint64_t& cur, uint64_t& iw0) {
     q.o = to_s(q.o); q.fl = to_s(q.fl); q.npend = to_s(q.npend); cur = to_s(cur); iw0 = to_s(iw0);
 }
 
+// ---- container members (ndfl_inflate_members_kernel) ------------------------------------------------
+// Lane 0 parses a member's header and trailer through the bounds-checked In view of the WHOLE item
+// (stream_in of in_off, in_len): byte i of the item, to be read only after i < in_len has been
+// checked, so no byte of the neighbour is acted on and In::ld never returns a word past the item's
+// last one.  Statuses are the public codes (the containers' Reasons, 13..19, lie outside the
+// decoder's internal ones), NDFL_E_ARG, or 0.
+__device__ __forceinline__ uint32_t item_byte(const In& all, uint64_t mis, uint64_t i) {
+    const uint64_t b = mis + i;
+    return (all.ld(b >> 2) >> (8 * (uint32_t)(b & 3))) & 0xFFu;
+}
+
+// ZlibMetadata.read (D/ZlibMetadata.java:47-80), its checks in its order; hl = the header's length.
+__device__ __forceinline__ int32_t parse_zlib_header(const In& all, uint64_t mis, uint64_t len, uint64_t& hl) {
+    if (len < 2) return NDFL_UNEXPECTED_END_OF_STREAM;
+    const uint32_t cmf = item_byte(all, mis, 0), flg = item_byte(all, mis, 1);
+    if (((cmf << 8) | flg) % 31u != 0) return NDFL_HEADER_CHECKSUM_MISMATCH;
+    const uint32_t cm = cmf & 15u;
+    if (cm != 8 && cm != 15) return NDFL_UNSUPPORTED_COMPRESSION_METHOD;
+    uint64_t i = 2;
+    if (flg & 0x20u) {                          // FDICT: the 4-byte dictionary id is skipped
+        if (len < 6) return NDFL_UNEXPECTED_END_OF_STREAM;
+        i = 6;
+    }
+    if (cm == 8 && (cmf >> 4) > 7) return NDFL_E_ARG;     // the record constructor's IllegalArgumentException
+    hl = i;
+    return 0;
+}
+
+// GzipMetadata.read (D/GzipMetadata.java:73-146), its checks in its order.  The header CRC (FHCRC:
+// the low 16 bits of the CRC-32 of every header byte before it) is taken bytewise as the bytes pass.
+__device__ __forceinline__ int32_t parse_gzip_header(const In& all, uint64_t mis, uint64_t len, uint64_t& hl) {
+    if (len < 2) return NDFL_UNEXPECTED_END_OF_STREAM;
+    if (item_byte(all, mis, 0) != 0x1Fu || item_byte(all, mis, 1) != 0x8Bu) return NDFL_GZIP_INVALID_MAGIC_NUMBER;
+    if (len < 3) return NDFL_UNEXPECTED_END_OF_STREAM;
+    if (item_byte(all, mis, 2) != 8u) return NDFL_UNSUPPORTED_COMPRESSION_METHOD;
+    if (len < 4) return NDFL_UNEXPECTED_END_OF_STREAM;
+    const uint32_t flg = item_byte(all, mis, 3);
+    if (flg & 0xE0u) return NDFL_GZIP_RESERVED_FLAGS_SET;
+    if (len < 10) return NDFL_UNEXPECTED_END_OF_STREAM;          // MTIME (4), XFL, OS
+    const uint32_t os = item_byte(all, mis, 9);
+    if (!(os < 14 || os == 255)) return NDFL_GZIP_UNSUPPORTED_OPERATING_SYSTEM;
+    const bool hcrc = (flg & 2u) != 0;
+    uint32_t hc = 0xFFFFFFFFu;
+    uint64_t i = 0;
+    // the next byte, i < len checked by the caller
+    auto take = [&]() { const uint32_t b = item_byte(all, mis, i++); if (hcrc) hc = crc_byte(hc, b); return b; };
+    if (hcrc) while (i < 10) take();
+    i = 10;
+    if (flg & 4u) {                             // FEXTRA
+        if (len - i < 2) return NDFL_UNEXPECTED_END_OF_STREAM;
+        uint64_t xl = take();
+        xl |= (uint64_t)take() << 8;
+        if (len - i < xl) return NDFL_UNEXPECTED_END_OF_STREAM;
+        if (hcrc) for (uint64_t k = 0; k < xl; k++) take();
+        else i += xl;
+    }
+    for (uint32_t f = 8u; f <= 16u; f <<= 1)    // FNAME, FCOMMENT: each to its 0 byte
+        if (flg & f)
+            for (;;) {
+                if (i >= len) return NDFL_UNEXPECTED_END_OF_STREAM;
+                if (take() == 0) break;
+            }
+    if (hcrc) {
+        if (len - i < 2) return NDFL_UNEXPECTED_END_OF_STREAM;
+        const uint32_t expect = ~hc & 0xFFFFu;
+        uint32_t actual = item_byte(all, mis, i);
+        actual |= item_byte(all, mis, i + 1) << 8;
+        i += 2;
+        if (actual != expect) return NDFL_HEADER_CHECKSUM_MISMATCH;
+    }
+    hl = i;
+    return 0;
+}
+
+// The trailer at byte t of the item, after a decode without a Reason: zlib's big-endian Adler-32
+// (D/ZlibInputStream.java:57-79), gzip's CRC-32 then ISIZE, the checksum tested first
+// (D/GzipInputStream.java:76-87).  `sum` is the finished checksum of all `total` output bytes.
+// Returns the Reason or 0; tl = the trailer's length.
+__device__ __forceinline__ int32_t check_trailer(const In& all, uint64_t mis, uint64_t len, uint32_t fmt, uint64_t t,
+                                                 uint32_t sum, uint64_t total, uint32_t& tl) {
+    tl = fmt == NDFL_FMT_GZIP ? 8u : 4u;
+    if (len - t < tl) return NDFL_UNEXPECTED_END_OF_STREAM;
+    uint32_t v[2] = {0, 0};
+    for (uint32_t k = 0; k < tl; k++) {
+        const uint32_t b = item_byte(all, mis, t + k);
+        if (fmt == NDFL_FMT_GZIP) v[k >> 2] |= b << (8 * (k & 3));
+        else v[0] = v[0] << 8 | b;
+    }
+    if (v[0] != sum) return NDFL_DECOMPRESSED_CHECKSUM_MISMATCH;
+    if (fmt == NDFL_FMT_GZIP && v[1] != (uint32_t)total) return NDFL_DECOMPRESSED_SIZE_MISMATCH;
+    return 0;
+}
+
+template <bool M> struct Io { typedef ndfl_batch_item Item; typedef ndfl_batch_result Result; };
+template <> struct Io<true> { typedef ndfl_member_item Item; typedef ndfl_member_result Result; };
+
 }  // namespace bat
 
-// results[i].status: the decoder's internal Reason (R_*, the host maps it and derives the symbol),
-// NDFL_E_CAPACITY, or 0; out_len and consumed_bits as the C ABI documents them.
+// The two kernels share one stream loop, inflate_batch_loop.inc (see there why it is included text).
 extern "C" __global__ void __launch_bounds__(64)
 ndfl_inflate_batch_kernel(const uint32_t* w, uint8_t* out, const ndfl_batch_item* items, ndfl_batch_result* results,
                           uint32_t n, uint32_t* ticket) {
-    using namespace bat;
-    __shared__ __attribute__((aligned(16))) Shared S;
-    __shared__ __attribute__((aligned(16))) uint8_t ring[RING];
-    __shared__ uint32_t inw[IW];
-    __shared__ uint32_t s_ticket;
-    const int lane = threadIdx.x;
-    // The table build gets the lane index read back from LDS (S.kind_, which this kernel does not use
-    // otherwise): computed from threadIdx, the build's many lane masks and lane-derived constants are
-    // hoisted out of the stream loop and held -- spilled, 88 SGPRs -- across the token loop.
-    S.kind_[lane] = (uint8_t)lane;
-    uint32_t* scr = S.exit_;                    // the build's 64 words (this kernel has no rounds)
-    w = (const uint32_t*)to_v((uint64_t)(uintptr_t)w);
-    out = (uint8_t*)to_v((uint64_t)(uintptr_t)out);
-    items = (const ndfl_batch_item*)to_v((uint64_t)(uintptr_t)items);
-    results = (ndfl_batch_result*)to_v((uint64_t)(uintptr_t)results);
-    ticket = (uint32_t*)to_v((uint64_t)(uintptr_t)ticket);
-    n = to_v(n);
-    for (;;) {
-        __syncthreads();
-        if (lane == 0) s_ticket = atomicAdd(ticket, 1u);
-        __syncthreads();
-        // (the stream's constants -- its index, item, input view and region -- are parked in vector
-        // registers too, like the kernel's arguments: none of them is needed in the token loop's scalars)
-        const uint32_t si = to_v((uint32_t)s_ticket);
-        if (to_s(si) >= to_s(n)) break;
-        ndfl_batch_item it = items[si];
-        it.in_off = to_v(it.in_off); it.in_len = to_v(it.in_len);
-        it.out_off = to_v(it.out_off); it.out_cap = to_v(it.out_cap);
-        const In in = stream_in(w, it.in_off, it.in_len);
-        const uint64_t p0 = (it.in_off & 3) * 8;
-        Out q;
-        q.ring = ring;
-        q.obeg = (uint64_t)(uintptr_t)out + it.out_off;
-        q.oend = q.obeg + it.out_cap;
-        q.o = q.obeg; q.fl = q.obeg; q.npend = 0;
-        uint32_t pend = 0;                      // this lane's pending literal
-        uint64_t iw0 = NO_STAGE;                // first input word staged in inw
-        uint64_t cur = p0;
-        uint32_t reason = 0;
-        for (;;) {
-            park(q, cur, iw0);
-            for (uint32_t s = (uint32_t)lane; s < 320; s += 64) S.lens[s] = 0;
-            __syncthreads();
-            if (lane == 0) {
-                Hdr h;
-                parse_hdr_core(in, cur, S.lens, S.cl_tab, h);
-                hdr_to_shared(h, S);
-            }
-            __syncthreads();
-            reason = __builtin_amdgcn_readfirstlane(S.h_err);
-            if (reason) break;
-            const uint32_t btype = __builtin_amdgcn_readfirstlane(S.h_btype);
-            if (btype == 0) {
-                unpark(q, cur, iw0);
-                const uint64_t d0 = to_s(S.h_d0);
-                const bool bfinal = __builtin_amdgcn_readfirstlane(S.h_bfinal) != 0;
-                // stored: a wave-wide copy of the bytes the input still has, then the length check
-                flush_pending(q, pend, lane);
-                const uint64_t avail = (in.nbits - d0) / 8, ln = to_s(S.h_len);
-                const uint64_t take = min(avail, ln), ib = d0 >> 3;
-                for (uint64_t done = 0; done < take;) {
-                    const uint32_t chunk = (uint32_t)min(take - done, (uint64_t)STORED_STEP);
-                    make_room(q, chunk, lane);
-                    for (uint32_t i = (uint32_t)lane * 4; i < chunk; i += 256) {
-                        const uint64_t b = ib + done + i;
-                        const uint64_t two = ((uint64_t)in.ld((b >> 2) + 1) << 32) | in.ld(b >> 2);
-                        const uint32_t v = (uint32_t)(two >> (8 * (uint32_t)(b & 3)));
-#pragma unroll
-                        for (uint32_t k = 0; k < 4; k++)
-                            if (i + k < chunk) q.ring[(q.o + i + k) & RMASK] = (uint8_t)(v >> (8 * k));
-                    }
-                    q.o += chunk;
-                    done += chunk;
-                    wsync();
-                }
-                if (take < ln) { reason = R_UEOS; break; }
-                cur = d0 + 8 * ln;
-                if (bfinal) break;
-                continue;
-            }
-            const int bt = build_block_tables((LShared*)&S, (int)S.kind_[lane], (lu32*)scr);
-            reason = __builtin_amdgcn_readfirstlane((uint32_t)bt & 0xFFu);
-            if (reason) break;
-            const bool ed = __builtin_amdgcn_readfirstlane((uint32_t)bt & 0x100u) != 0;
-            unpark(q, cur, iw0);
-            const uint64_t d0 = to_s(S.h_d0);
-            const bool bfinal = __builtin_amdgcn_readfirstlane(S.h_bfinal) != 0;
-            // the wave-uniform token loop
-            uint64_t pos = d0;
-            bool eob = false;
-            while (!eob && !reason) {
-                const uint64_t wi = pos >> 5;
-                if (wi < iw0 || wi + 3 > iw0 + IW) {
-                    wsync();                    // the reads of the words staged before
-                    iw0 = wi;
-#pragma unroll
-                    for (uint32_t k = 0; k < IW / 64; k++) inw[k * 64 + lane] = in.ld(iw0 + k * 64 + lane);
-                    wsync();
-                }
-                const uint32_t r = (uint32_t)(wi - iw0), sh = (uint32_t)pos & 31;
-                const uint32_t wa = inw[r], wb = inw[r + 1], wc = inw[r + 2];
-                const uint32_t lo = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_alignbit(wb, wa, sh));
-                const uint32_t hi = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_alignbit(wc, wb, sh));
-                const uint32_t e = __builtin_amdgcn_readfirstlane(S.t.lit[lo & ((1u << LB) - 1u)]);
-                const uint32_t nb = (uint32_t)min(in.nbits - pos, (uint64_t)0xFFFFFFFFu);
-                uint32_t adv = 0;
-                Tok tk;
-                tok_e<true>(lo, hi, e, adv, S.t, ed, 0xFFFFFFFFu, nb, tk);
-                const uint32_t kind = __builtin_amdgcn_readfirstlane(tk.kind);
-                const uint32_t val = __builtin_amdgcn_readfirstlane(tk.val);
-                const uint32_t tn = __builtin_amdgcn_readfirstlane(tk.n);
-                const uint32_t dist = __builtin_amdgcn_readfirstlane(tk.dist);
-                pos += to_s(adv);
-                if (kind == K_LIT) {
-                    add_literal(q, pend, val & 0xFFu, lane);
-                    if (tn == 2) add_literal(q, pend, (val >> 8) & 0xFFu, lane);
-                } else if (kind == K_LEN) {
-                    flush_pending(q, pend, lane);
-                    if (dist > q.o - q.obeg) reason = R_COPY_BEFORE;
-                    else copy_run(q, tn, dist, lane);
-                } else if (kind == K_EOB) {
-                    eob = true;
-                } else {
-                    reason = val;
-                }
-            }
-            if (reason) break;
-            cur = pos;
-            if (bfinal) break;
-        }
-        unpark(q, cur, iw0);
-        flush_pending(q, pend, lane);
-        flush_to(q, q.o, lane);
-        if (lane == 0) {
-            const uint64_t total = q.o - q.obeg;
-            ndfl_batch_result rr;
-            rr.status = reason ? (int32_t)reason : total > it.out_cap ? NDFL_E_CAPACITY : 0;
-            rr.error_symbol = -1;
-            rr.out_len = total;
-            rr.consumed_bits = reason ? 0 : cur - p0;
-            results[si] = rr;
-        }
-    }
+#define NDFL_BATCH_MEMBERS 0
+#include "inflate_batch_loop.inc"
+#undef NDFL_BATCH_MEMBERS
+}
+
+// crc_x: the context's x^(8k) tables (d_tabs + 1024 words), read-only.
+extern "C" __global__ void __launch_bounds__(64)
+ndfl_inflate_members_kernel(const uint32_t* w, uint8_t* out, const ndfl_member_item* items, ndfl_member_result* results,
+                            uint32_t n, uint32_t* ticket, const uint32_t* crc_x) {
+#define NDFL_BATCH_MEMBERS 1
+#include "inflate_batch_loop.inc"
+#undef NDFL_BATCH_MEMBERS
 }
 
 // ---- host side ------------------------------------------------------------------------------------
@@ -334,14 +398,19 @@ struct BatchScratch {
 // The batch on stream s (arguments already validated): one launch, one host sync.  results[i].status
 // comes back as the kernel wrote it (internal Reason codes; the C ABI maps them).  Host output goes
 // through a device staging buffer and only each stream's stored bytes are copied into `out`.
+// M: ndfl_inflate_members (its items, results and kernel; crc_x = the context's x^(8k) tables).
+template <bool M>
 static int inflate_batch_run(InflateScratch& S, BatchScratch& B, hipStream_t s, hipEvent_t e0, hipEvent_t e1,
-                             const uint8_t* in, uint64_t in_size, uint8_t* out, const ndfl_batch_item* items,
-                             ndfl_batch_result* results, uint32_t n, uint32_t flags, double* last_ms) {
+                             const uint8_t* in, uint64_t in_size, uint8_t* out, const typename bat::Io<M>::Item* items,
+                             typename bat::Io<M>::Result* results, uint32_t n, uint32_t flags, double* last_ms,
+                             const uint32_t* crc_x = nullptr) {
+    typedef typename bat::Io<M>::Item Item;
+    typedef typename bat::Io<M>::Result Result;
     const uint32_t* d_w = nullptr;
     INF_RC(stage_input(S, s, in, in_size, flags, &d_w));
-    const size_t items_b = (size_t)n * sizeof(ndfl_batch_item), res_b = (size_t)n * sizeof(ndfl_batch_result);
+    const size_t items_b = (size_t)n * sizeof(Item), res_b = (size_t)n * sizeof(Result);
     INF_CHK(inf_ensure(&B.d_items, &B.d_items_cap, items_b + res_b + 16));
-    ndfl_batch_result* d_res = (ndfl_batch_result*)((char*)B.d_items + items_b);
+    Result* d_res = (Result*)((char*)B.d_items + items_b);
     uint32_t* d_ticket = (uint32_t*)((char*)d_res + res_b);
     INF_CHK(hipMemcpyAsync(B.d_items, items, items_b, hipMemcpyHostToDevice, s));
     INF_CHK(hipMemsetAsync(d_ticket, 0, 16, s));
@@ -359,13 +428,19 @@ static int inflate_batch_run(InflateScratch& S, BatchScratch& B, hipStream_t s, 
         if (hi > lo) INF_CHK(inf_ensure(&B.d_out, &B.d_out_cap, hi - lo));
         d_out = (uint8_t*)B.d_out - (hi > lo ? lo : 0);
     }
-    static const uint32_t auto_grid = wave_grid(ndfl_inflate_batch_kernel, 256 * 16);
+    static const uint32_t auto_grid = M ? wave_grid(ndfl_inflate_members_kernel, 256 * 16)
+                                        : wave_grid(ndfl_inflate_batch_kernel, 256 * 16);
     uint32_t grid = std::min(n, auto_grid);
     if (S.knobs.batch_waves) grid = std::min(grid, S.knobs.batch_waves);
-    if (S.knobs.stats) fprintf(stderr, "[ndfl] inflate batch: %u streams, %u waves (of %u)\n", n, grid, auto_grid);
+    if (S.knobs.stats) fprintf(stderr, "[ndfl] inflate %s: %u streams, %u waves (of %u)\n", M ? "members" : "batch", n, grid,
+                               auto_grid);
     INF_CHK(hipEventRecord(e0, s));
-    hipLaunchKernelGGL(ndfl_inflate_batch_kernel, dim3(grid), dim3(64), 0, s, d_w, d_out, (const ndfl_batch_item*)B.d_items,
-                       d_res, n, d_ticket);
+    if constexpr (M)
+        hipLaunchKernelGGL(ndfl_inflate_members_kernel, dim3(grid), dim3(64), 0, s, d_w, d_out, (const Item*)B.d_items, d_res,
+                           n, d_ticket, crc_x);
+    else
+        hipLaunchKernelGGL(ndfl_inflate_batch_kernel, dim3(grid), dim3(64), 0, s, d_w, d_out, (const Item*)B.d_items, d_res,
+                           n, d_ticket);
     INF_CHK(hipGetLastError());
     INF_CHK(hipEventRecord(e1, s));
     INF_CHK(hipMemcpyAsync(results, d_res, res_b, hipMemcpyDeviceToHost, s));

@@ -31,7 +31,7 @@ struct Knobs {
     uint32_t flat_min = 49152;   // NDFL_FLAT_MIN: chains to count at least for flat groups (their latency)
     bool test_segflip = false;   // NDFL_TEST_SEGFLIP: one count-pass record's byte count perturbed
                                  //   before the emit pass (the emit-side check must fail the decode)
-    uint32_t batch_waves = 0;    // NDFL_BATCH_WAVES: cap of ndfl_inflate_batch's grid (0: automatic); the
+    uint32_t batch_waves = 0;    // NDFL_BATCH_WAVES: cap of ndfl_inflate_batch's / _members' grid (0: automatic); the
                                  //   tests put many streams on one wave with it
     void read() {
         auto on = [](const char* n) { const char* e = getenv(n); return e && strcmp(e, "0") != 0; };

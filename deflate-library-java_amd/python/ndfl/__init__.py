@@ -19,6 +19,7 @@ import sys
 
 from . import _lib
 from ._lib import IN_DEVICE, OUT_DEVICE, DICT_DEFERRED, IN_PADDED, IN_PAD_BYTES, IN_PARTIAL, NEED_INPUT, NO_END, STRATEGIES, NdflError, check, load, reason_name
+from ._lib import FMT_RAW, FMT_ZLIB, FMT_GZIP, SUM_NONE, SUM_CRC32, SUM_ADLER32
 
 __all__ = ["Context", "Reason", "DataFormatException", "Lz77Huffman", "Uncompressed", "MultiStrategy", "BinarySplit", "DeflaterOutputStream", "InflaterInputStream", "BitOutputStream",
            "GzipMetadata", "GzipOutputStream", "GzipInputStream", "ZlibMetadata", "ZlibOutputStream",
@@ -392,6 +393,58 @@ class Context:
                     continue
                 check(code, "ndfl_inflate_batch")
                 done[i] = (None if code == 0 else Reason(code - 1), ctypes.string_at(ctypes.addressof(out) + it[2], min(olen, it[3])), bits)
+            todo = again
+        return done
+
+    def inflate_members_raw(self, in_addr, in_size, out_addr, out_size, items, flags):
+        """ndfl_inflate_members: `items` is a sequence of (in_off, in_len, out_off, out_cap, format, sum)
+        with format a FMT_* and sum a SUM_* (read for FMT_RAW only).  Returns one (code, error_symbol,
+        out_len, consumed_bits, checksum, header_len) per stream; code = 0 / Reason+1 / E_CAPACITY /
+        E_ARG (a zlib header whose CINFO the reference's ZlibMetadata refuses)."""
+        L = load()
+        self._order()
+        n = len(items)
+        arr = (_lib.MemberItem * max(1, n))(*[_lib.MemberItem(*map(int, it)) for it in items])
+        res = (_lib.MemberResult * max(1, n))()
+        check(L.ndfl_inflate_members(self._h, in_addr, in_size, out_addr, out_size, arr, res, n, flags),
+              "ndfl_inflate_members")
+        return [(r.status, r.error_symbol, r.out_len, r.consumed_bits, r.checksum, r.header_len) for r in res[:n]]
+
+    def inflate_members(self, streams, format, sum=None, out_caps=None):
+        """Decode many zlib members (FMT_ZLIB), gzip members (FMT_GZIP: one member per stream) or raw
+        DEFLATE streams (FMT_RAW, with `sum` = SUM_CRC32 / SUM_ADLER32 / None) held in host bytes, in one
+        call, checksums verified on the GPU.  `format` is one FMT_* for all streams or one per stream.
+        Returns one (reason|None, bytes, consumed_bits, checksum, header_len) per stream; consumed_bits / 8
+        is a container member's whole length.  Capacities as in inflate_batch: with out_caps a stream that
+        needs more raises NdflError(E_CAPACITY); without, every region is 4 * len + 65536 bytes and only
+        the streams that overflowed are run again, with the size they reported."""
+        streams = [bytes(s) for s in streams]
+        n = len(streams)
+        fmts = [int(format)] * n if isinstance(format, int) else [int(f) for f in format]
+        kind = _lib.SUM_NONE if sum is None else int(sum)
+        done = [None] * n
+        todo = list(range(n))
+        caps = [4 * len(s) + 65536 for s in streams] if out_caps is None else [int(c) for c in out_caps]
+        while todo:
+            packed = b"".join(streams[i] for i in todo)
+            src = ctypes.create_string_buffer(packed, max(1, len(packed)))
+            items, in_off, out_off = [], 0, 0
+            for i in todo:
+                items.append((in_off, len(streams[i]), out_off, caps[i], fmts[i], kind))
+                in_off += len(streams[i])
+                out_off += caps[i]
+            out = ctypes.create_string_buffer(max(1, out_off))
+            res = self.inflate_members_raw(ctypes.addressof(src), len(packed), ctypes.addressof(out), out_off, items, 0)
+            again = []
+            for i, it, r in zip(todo, items, res):
+                code, _, olen, bits, checksum, header_len = r
+                if code == _lib.E_CAPACITY and out_caps is None:
+                    caps[i] = olen
+                    again.append(i)
+                    continue
+                check(code, "ndfl_inflate_members")
+                done[i] = (None if code == 0 else Reason(code - 1),
+                           ctypes.string_at(ctypes.addressof(out) + it[2], min(olen, it[3])), bits, checksum, header_len)
             todo = again
         return done
 

@@ -40,7 +40,11 @@ EXPORTS = ["ndfl_abi_version", "ndfl_error_string", "ndfl_ctx_create", "ndfl_ctx
            "ndfl_inflate", "ndfl_inflate_range", "ndfl_inflate_resolve", "ndfl_bits_shift", "ndfl_crc32", "ndfl_adler32",
            "ndfl_crc32_combine", "ndfl_decide", "ndfl_compress_to", "ndfl_decision_free", "ndfl_inflate_sync",
            "ndfl_inflate_tail", "ndfl_inflate_headers", "ndfl_inflate_tail_map", "ndfl_ctx_error_symbol",
-           "ndfl_inflate_batch"]
+           "ndfl_inflate_batch", "ndfl_inflate_members"]
+
+# ndfl_inflate_members: NDFL_FMT_* (an item's container) and NDFL_SUM_* (a raw item's checksum)
+FMT_RAW, FMT_ZLIB, FMT_GZIP = 0, 1, 2
+SUM_NONE, SUM_CRC32, SUM_ADLER32 = 0, 1, 2
 
 KIND_LZ77, KIND_UNCOMPRESSED = 0, 1
 
@@ -71,6 +75,20 @@ class BatchResult(ctypes.Structure):
     """ndfl_batch_result (include/ndfl.h)."""
     _fields_ = [("status", ctypes.c_int32), ("error_symbol", ctypes.c_int32),
                 ("out_len", ctypes.c_uint64), ("consumed_bits", ctypes.c_uint64)]
+
+
+class MemberItem(ctypes.Structure):
+    """ndfl_member_item (include/ndfl.h)."""
+    _fields_ = [("in_off", ctypes.c_uint64), ("in_len", ctypes.c_uint64),
+                ("out_off", ctypes.c_uint64), ("out_cap", ctypes.c_uint64),
+                ("format", ctypes.c_uint32), ("sum", ctypes.c_uint32)]
+
+
+class MemberResult(ctypes.Structure):
+    """ndfl_member_result (include/ndfl.h)."""
+    _fields_ = [("status", ctypes.c_int32), ("error_symbol", ctypes.c_int32),
+                ("out_len", ctypes.c_uint64), ("consumed_bits", ctypes.c_uint64),
+                ("checksum", ctypes.c_uint32), ("header_len", ctypes.c_uint32)]
 
 
 _lib = None
@@ -110,6 +128,11 @@ def load():
     if hasattr(L, "ndfl_inflate_batch"):
         L.ndfl_inflate_batch.argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(BatchItem),
                                          ctypes.POINTER(BatchResult), u32, u32]
+    # (likewise the members entry point: scripts/bench_batch.py --mode batch+sum measures its baseline
+    # on the build before it)
+    if hasattr(L, "ndfl_inflate_members"):
+        L.ndfl_inflate_members.argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(MemberItem),
+                                           ctypes.POINTER(MemberResult), u32, u32]
     L.ndfl_inflate_range.argtypes = [vp, vp, u64, u64, u64, vp, u64, u64, ctypes.POINTER(u64), ctypes.POINTER(u64),
                                      u32]
     L.ndfl_inflate_resolve.argtypes = [vp, ctypes.POINTER(u64)]

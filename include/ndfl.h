@@ -269,6 +269,78 @@ int ndfl_inflate_batch(ndfl_ctx* ctx, const uint8_t* in, uint64_t in_size, uint8
                        const ndfl_batch_item* items, ndfl_batch_result* results, uint32_t n, uint32_t flags);
 
 /*
+ * ndfl_inflate_batch for container members, with the checksum taken in the same launch: item i is a
+ * zlib member (ZlibInputStream: D/ZlibInputStream.java, header D/ZlibMetadata.java:47-80), ONE gzip
+ * member (GzipInputStream: D/GzipInputStream.java, header D/GzipMetadata.java:73-146), or a raw
+ * DEFLATE stream whose CRC-32 or Adler-32 the caller wants (a zip entry: its CRC-32 is in the
+ * directory).  Still one kernel launch and one host sync whatever n is: the header is parsed, the
+ * output checksummed on its way out of the decoder, and the trailer compared, by the wave that
+ * decodes the stream.  Buffers, items' regions, flags, stream ordering, ndfl_ctx_last_kernel_ms and
+ * the "no byte of `out` outside a stream's stored bytes is written" rule are ndfl_inflate_batch's.
+ *
+ * NDFL_FMT_RAW   status, error_symbol, out_len, consumed_bits and the stored bytes are exactly
+ *                ndfl_inflate_batch's for the same item.  checksum = the java.util.zip.CRC32 value
+ *                (NDFL_SUM_CRC32; initial 0) or the Adler-32 (NDFL_SUM_ADLER32; initial 1) of ALL out_len
+ *                decoded bytes, those past out_cap included: valid when status is 0 or NDFL_E_CAPACITY,
+ *                0 on a Reason and with NDFL_SUM_NONE.  header_len = 0.
+ * NDFL_FMT_ZLIB  the header checks are ZlibMetadata.read's, in its order (D/ZlibMetadata.java:47-80):
+ *                fewer than 2 bytes: UNEXPECTED_END_OF_STREAM; (CMF << 8 | FLG) % 31 != 0:
+ *                HEADER_CHECKSUM_MISMATCH; a method other than 8 or 15: UNSUPPORTED_COMPRESSION_METHOD
+ *                (15 is accepted and decoded as DEFLATE, as the reference does); FDICT: 4 more bytes
+ *                are skipped (UNEXPECTED_END_OF_STREAM if absent; the dictionary stays empty); method 8
+ *                with CINFO > 7 is the record constructor's IllegalArgumentException: this stream's
+ *                status is NDFL_E_ARG, its out_len 0.  The DEFLATE data is decoded as for RAW; the 4
+ *                trailer bytes follow at header_len + ceil(bits / 8) (fewer: UNEXPECTED_END_OF_STREAM)
+ *                and hold the big-endian Adler-32 of the output, else DECOMPRESSED_CHECKSUM_MISMATCH
+ *                (D/ZlibInputStream.java:57-79).
+ * NDFL_FMT_GZIP  the header checks are GzipMetadata.read's, in its order (D/GzipMetadata.java:73-146):
+ *                magic (GZIP_INVALID_MAGIC_NUMBER), method != 8 (UNSUPPORTED_COMPRESSION_METHOD),
+ *                flags & 0xE0 (GZIP_RESERVED_FLAGS_SET), MTIME (4 bytes), XFL, an OS byte that is neither
+ *                < 14 nor 255 (GZIP_UNSUPPORTED_OPERATING_SYSTEM), FEXTRA (2-byte little-endian length,
+ *                then that many bytes), FNAME and FCOMMENT (each to a 0 byte), FHCRC (the low 16 bits of
+ *                the CRC-32 of all header bytes before it, else HEADER_CHECKSUM_MISMATCH); a missing byte
+ *                anywhere is UNEXPECTED_END_OF_STREAM.  The DEFLATE data is decoded as for RAW; 8 trailer
+ *                bytes follow (fewer: UNEXPECTED_END_OF_STREAM): a CRC-32 that differs from the output's
+ *                is DECOMPRESSED_CHECKSUM_MISMATCH, otherwise (uint32_t)out_len != ISIZE is
+ *                DECOMPRESSED_SIZE_MISMATCH -- the checksum is tested first (D/GzipInputStream.java:76-87).
+ * Both containers: `sum` is not read.  checksum = the value computed over the output, valid as for RAW
+ * and on the two mismatch Reasons.  header_len = the bytes before the DEFLATE data once the header is
+ * accepted, else 0.  On status 0 consumed_bits = 8 x the member's length in bytes (header,
+ * ceil(bits / 8), trailer), so in_off + consumed_bits / 8 is the next member of a concatenation; bytes
+ * after the trailer are ignored.  out_len is 0 on a header error; on a trailer error it is the whole
+ * decoded length, and those bytes are stored.  DEFLATE errors report as for RAW, with error_symbol.
+ * Precedence as in ndfl_inflate_batch: a Reason, or the per-stream NDFL_E_ARG, wins over
+ * NDFL_E_CAPACITY -- the checksum covers the bytes past out_cap, so a member that overflows its region
+ * AND has a bad trailer reports the mismatch.
+ * Returns as ndfl_inflate_batch; in addition NDFL_E_ARG when an item's format > 2 or sum > 2 (nothing
+ * is decoded).
+ * Against ndfl_inflate_batch followed by one ndfl_crc32 / ndfl_adler32 call per stream (measured on
+ * one MI355X, DESIGN.md §4 "Batched inflate of container members"): 65,536 x 512 B take 13.0 to 13.9 ms
+ * instead of 4.7 to 5.3 s, 4,096 x 4 KiB 4.2 to 4.3 ms instead of 290 to 347 ms, 256 x 1 MiB 136 to
+ * 137 ms instead of 155 to 164 ms.  The kernel's time against ndfl_inflate_batch's on the same streams:
+ * Adler-32 within +-1.6 %, CRC-32 +0.3 to +0.6 % from 4 KiB streams up and +4.7 to +5.5 % on 512-byte
+ * streams.  The crossover to ndfl_inflate is ndfl_inflate_batch's.
+ */
+#define NDFL_FMT_RAW   0u   /* raw DEFLATE, as ndfl_inflate_batch */
+#define NDFL_FMT_ZLIB  1u   /* ZlibInputStream (D/ZlibInputStream.java, D/ZlibMetadata.java:47-80) */
+#define NDFL_FMT_GZIP  2u   /* GzipInputStream, one member (D/GzipInputStream.java, D/GzipMetadata.java:73-146) */
+#define NDFL_SUM_NONE    0u
+#define NDFL_SUM_CRC32   1u
+#define NDFL_SUM_ADLER32 2u
+typedef struct {
+    uint64_t in_off, in_len, out_off, out_cap;   /* as ndfl_batch_item */
+    uint32_t format;                             /* NDFL_FMT_* */
+    uint32_t sum;                                /* NDFL_SUM_*: read for NDFL_FMT_RAW only */
+} ndfl_member_item;                              /* 40 bytes */
+typedef struct {
+    int32_t  status, error_symbol;               /* as ndfl_batch_result (status also NDFL_E_ARG: zlib CINFO > 7) */
+    uint64_t out_len, consumed_bits;
+    uint32_t checksum, header_len;
+} ndfl_member_result;                            /* 32 bytes */
+int ndfl_inflate_members(ndfl_ctx* ctx, const uint8_t* in, uint64_t in_size, uint8_t* out, uint64_t out_size,
+                         const ndfl_member_item* items, ndfl_member_result* results, uint32_t n, uint32_t flags);
+
+/*
  * Decompress the block-aligned bit range [start_bit, end_bit) of one raw DEFLATE stream: one GPU's
  * shard of a stream decoded across GPUs, or one batch of a stream read incrementally
  * (NDFL_IN_PARTIAL, end_bit UINT64_MAX: InflaterInputStream's bounded input buffer,

@@ -1,6 +1,14 @@
 #!/usr/bin/env python3
 """Many independent raw DEFLATE streams: one ndfl_inflate call per stream (--mode loop) against one
-ndfl_inflate_batch call (--mode batch).  Not bench.py: this measures the batch entry point only.
+ndfl_inflate_batch call (--mode batch).  Not bench.py: this measures the batch entry points only.
+
+Container members and checksums (--format zlib | gzip | raw-crc): one ndfl_inflate_members call
+(--mode members: header, decode, checksum and trailer check in one launch) against what a caller had
+to do before it (--mode batch+sum): one ndfl_inflate_batch call on the DEFLATE data -- the header
+lengths handed to it for nothing -- and then one ndfl_adler32 (zlib) or ndfl_crc32 (gzip, raw-crc)
+call per stream on the device-resident output.  The members are the same streams in a 2-byte zlib
+or 10-byte gzip header and their trailer.  --mode takes a comma-separated list (the streams of a
+shape are made once).
 
 Inputs are seeded word-salad text (as tests/test_gpu_inflate.py::test_zlib_streams), compressed with
 Python's zlib, raw (wbits=-15), in three shapes: 65,536 x 512 B, 4,096 x 4 KiB, 256 x 1 MiB.  Inputs
@@ -11,13 +19,16 @@ return), median of --reps after --warmup, one JSON line per shape.  The first pa
 output byte against the original data.
 
 --mode loop needs only ndfl_inflate, so it also runs on a build without the batch entry point
-(NDFL_LIB_PATH selects the library): that is the baseline.
+(NDFL_LIB_PATH selects the library): that is the baseline.  Likewise --mode batch+sum runs on a build
+without ndfl_inflate_members.
 """
 import argparse
+import ctypes
 import json
 import os
 import random
 import statistics
+import struct
 import sys
 import time
 import zlib
@@ -45,9 +56,22 @@ def make_streams(name, seed):
     return datas, comps
 
 
+def wrap(fmt, raw, data):
+    """(member bytes, header length, the checksum its trailer holds) of one stream in --format fmt."""
+    if fmt == "zlib":
+        a = zlib.adler32(data)
+        return b"\x78\x9c" + raw + a.to_bytes(4, "big"), 2, a
+    c = zlib.crc32(data)
+    if fmt == "gzip":
+        return b"\x1f\x8b\x08\x00\x00\x00\x00\x00\x00\x03" + raw + struct.pack("<II", c, len(data) & 0xFFFFFFFF), 10, c
+    return raw, 0, c
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=["loop", "batch"], required=True)
+    ap.add_argument("--mode", required=True, help="comma-separated: loop, batch, members, batch+sum")
+    ap.add_argument("--format", choices=["zlib", "gzip", "raw-crc"], default="zlib",
+                    help="members / batch+sum: the container of each stream")
     ap.add_argument("--shapes", default=",".join(SHAPES))
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
@@ -59,61 +83,97 @@ def main():
     ctx = ndfl.Context(0)
     ctx.set_stream(torch.cuda.current_stream().cuda_stream)
     flags = ndfl.IN_DEVICE | ndfl.OUT_DEVICE | ndfl.IN_PADDED
+    modes = a.mode.split(",")
+    assert all(m in ("loop", "batch", "members", "batch+sum") for m in modes), modes
+    L = ndfl._lib.load()
     for name in a.shapes.split(","):
         n, size = SHAPES[name]
         datas, comps = make_streams(name, a.seed)
-        in_offs, off = [], 0
-        for c in comps:
-            in_offs.append(off)
-            off += (len(c) + ndfl.IN_PAD_BYTES + 15) // 16 * 16
-        host = bytearray(off + 16)
-        for o, c in zip(in_offs, comps):
-            host[o:o + len(c)] = c
-        d_in = torch.frombuffer(host, dtype=torch.uint8).cuda()
-        d_out = torch.zeros(n * size, dtype=torch.uint8, device="cuda")
-        pi, po = d_in.data_ptr(), d_out.data_ptr()
-        items = [(in_offs[i], len(comps[i]), i * size, size) for i in range(n)]
         want = b"".join(datas)
+        for mode in modes:
+            contained = mode in ("members", "batch+sum")
+            fmt = a.format if contained else "raw"
+            packed = [wrap(fmt, c, d) for c, d in zip(comps, datas)] if contained else [(c, 0, 0) for c in comps]
+            in_offs, off = [], 0
+            for m, _, _ in packed:
+                in_offs.append(off)
+                off += (len(m) + ndfl.IN_PAD_BYTES + 15) // 16 * 16
+            host = bytearray(off + 16)
+            for o, (m, _, _) in zip(in_offs, packed):
+                host[o:o + len(m)] = m
+            d_in = torch.frombuffer(host, dtype=torch.uint8).cuda()
+            d_out = torch.zeros(n * size, dtype=torch.uint8, device="cuda")
+            pi, po = d_in.data_ptr(), d_out.data_ptr()
+            # the batch's view: the DEFLATE data alone (behind the header, which batch+sum is told for nothing)
+            items = [(in_offs[i] + packed[i][1], len(comps[i]), i * size, size) for i in range(n)]
+            sums = [0] * n
 
-        # the batch goes straight to the C ABI with its item and result arrays built once (the
-        # Python wrapper's per-item conversions would be most of the small shapes' time)
-        L = ndfl._lib.load()
-        if a.mode == "batch":
-            arr = (ndfl._lib.BatchItem * n)(*[ndfl._lib.BatchItem(*it) for it in items])
-            res = (ndfl._lib.BatchResult * n)()
+            # the batches go straight to the C ABI with their item and result arrays built once (the
+            # Python wrapper's per-item conversions would be most of the small shapes' time)
+            if mode in ("batch", "batch+sum"):
+                arr = (ndfl._lib.BatchItem * n)(*[ndfl._lib.BatchItem(*it) for it in items])
+                res = (ndfl._lib.BatchResult * n)()
+            if mode == "members":
+                f, k = {"zlib": (ndfl._lib.FMT_ZLIB, 0), "gzip": (ndfl._lib.FMT_GZIP, 0),
+                        "raw-crc": (ndfl._lib.FMT_RAW, ndfl._lib.SUM_CRC32)}[fmt]
+                arr = (ndfl._lib.MemberItem * n)(*[ndfl._lib.MemberItem(in_offs[i], len(packed[i][0]), i * size, size, f, k)
+                                                   for i in range(n)])
+                res = (ndfl._lib.MemberResult * n)()
+            sum_call = L.ndfl_adler32 if fmt == "zlib" else L.ndfl_crc32
+            sum_init = 1 if fmt == "zlib" else 0
 
-        def once():
-            if a.mode == "batch":
-                rc = L.ndfl_inflate_batch(ctx._h, pi, len(host), po, n * size, arr, res, n, flags)
-                assert rc == 0, rc
-                return ctx.last_kernel_ms()
-            for io, il, oo, oc in items:
-                r, olen, _ = ctx.inflate_raw(pi + io, il, po + oo, oc, flags)
-                assert r == 0 and olen == size
-            return None
+            def once():
+                if mode == "members":
+                    rc = L.ndfl_inflate_members(ctx._h, pi, len(host), po, n * size, arr, res, n, flags)
+                    assert rc == 0, rc
+                    return ctx.last_kernel_ms()
+                if mode in ("batch", "batch+sum"):
+                    rc = L.ndfl_inflate_batch(ctx._h, pi, len(host), po, n * size, arr, res, n, flags)
+                    assert rc == 0, rc
+                    kms = ctx.last_kernel_ms()
+                    if mode == "batch+sum":
+                        v = ctypes.c_uint32()
+                        for i in range(n):
+                            v.value = sum_init
+                            rc = sum_call(ctx._h, ctypes.byref(v), po + i * size, res[i].out_len, ndfl.IN_DEVICE)
+                            assert rc == 0, rc
+                            sums[i] = v.value
+                    return kms
+                for io, il, oo, oc in items:
+                    r, olen, _ = ctx.inflate_raw(pi + io, il, po + oo, oc, flags)
+                    assert r == 0 and olen == size
+                return None
 
-        times, kms = [], None
-        for it in range(a.warmup + a.reps):
-            d_out.zero_()
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            kms = once()
-            torch.cuda.synchronize()
-            dt = (time.perf_counter() - t0) * 1e3
-            if it == 0:
-                assert bytes(d_out.cpu().numpy()) == want, "decoded bytes differ"
-                if a.mode == "batch":
-                    assert all(r.status == 0 and r.out_len == size for r in res)
-            if it >= a.warmup:
-                times.append(dt)
-        med = statistics.median(times)
-        line = {"bench": "batch_inflate", "label": a.label, "mode": a.mode, "shape": name, "streams": n,
-                "stream_bytes": size, "in_bytes": sum(map(len, comps)), "out_bytes": n * size,
-                "ms_median": round(med, 3), "ms_all": [round(t, 3) for t in times],
-                "out_MBps": round(n * size / med / 1e3, 1)}
-        if kms is not None:
-            line["kernel_ms_last"] = round(kms, 3)
-        print(json.dumps(line), flush=True)
+            times, kms = [], None
+            for it in range(a.warmup + a.reps):
+                d_out.zero_()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                kms = once()
+                torch.cuda.synchronize()
+                dt = (time.perf_counter() - t0) * 1e3
+                if it == 0:
+                    assert bytes(d_out.cpu().numpy()) == want, "decoded bytes differ"
+                    if mode != "loop":
+                        assert all(r.status == 0 and r.out_len == size for r in res)
+                    if mode == "members":
+                        # (a raw stream's consumed_bits end inside its last byte, a member's are its length)
+                        assert all(r.checksum == m[2] and (r.consumed_bits + 7) // 8 == len(m[0]) for r, m in zip(res, packed))
+                    if mode == "batch+sum":
+                        assert sums == [m[2] for m in packed], "checksums differ"
+                if it >= a.warmup:
+                    times.append(dt)
+            med = statistics.median(times)
+            line = {"bench": "batch_inflate", "label": a.label, "mode": mode, "shape": name, "streams": n,
+                    "stream_bytes": size, "in_bytes": sum(len(m[0]) for m in packed), "out_bytes": n * size,
+                    "ms_median": round(med, 3), "ms_all": [round(t, 3) for t in times],
+                    "out_MBps": round(n * size / med / 1e3, 1)}
+            if contained:
+                line["format"] = fmt
+            if kms is not None:
+                line["kernel_ms_last"] = round(kms, 3)
+            print(json.dumps(line), flush=True)
+            del d_in, d_out
 
 
 if __name__ == "__main__":
