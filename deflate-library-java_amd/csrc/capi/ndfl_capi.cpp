@@ -7,6 +7,7 @@
 #include "../hip/strategy_kernels.hip"
 #include "../hip/inflate_kernels.hip"
 #include "../hip/inflate_batch.hip"
+#include "../hip/deflate_batch.hip"
 
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -1072,6 +1073,33 @@ int ndfl_inflate_members(ndfl_ctx* c, const uint8_t* in, uint64_t in_size, uint8
                                           results, n, flags, &c->last_ms, c->d_tabs.as<uint32_t>() + 1024);
     if (r) return r == -4 ? NDFL_E_DEVICE : NDFL_E_INTERNAL;
     batch_public_reasons(results, n);
+    return NDFL_OK;
+}
+
+int ndfl_deflate_batch(ndfl_ctx* c, const uint8_t* in, uint64_t in_size, uint8_t* out, uint64_t out_size,
+                       const ndfl_member_item* items, ndfl_deflate_result* results, uint32_t n, int strategy,
+                       uint32_t chunk_len, uint32_t hist_limit, uint32_t flags) {
+    if (!c) return NDFL_E_ARG;
+    if (n == 0) return NDFL_OK;
+    int rle, dyn;
+    switch (strategy) {
+        case NDFL_LITERAL_STATIC: rle = 0; dyn = 0; break;
+        case NDFL_LITERAL_DYNAMIC: rle = 0; dyn = 1; break;
+        case NDFL_RLE_STATIC: rle = 1; dyn = 0; break;
+        case NDFL_RLE_DYNAMIC: rle = 1; dyn = 1; break;
+        case NDFL_FULL_STATIC: case NDFL_FULL_DYNAMIC: case NDFL_UNCOMPRESSED: return NDFL_E_UNSUPPORTED;
+        default: return NDFL_E_ARG;
+    }
+    if (chunk_len == 0 || hist_limit > 32768) return NDFL_E_ARG;
+    if (chunk_len > (uint32_t)MAX_CHUNK) return NDFL_E_UNSUPPORTED;
+    if (!batch_regions_valid(in, in_size, out, out_size, items, results, n)) return NDFL_E_ARG;
+    for (uint32_t i = 0; i < n; i++)
+        if (items[i].format > NDFL_FMT_GZIP || items[i].sum > NDFL_SUM_ADLER32) return NDFL_E_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    const int r = deflate_batch_run(c->batch, &c->d_in.p, &c->d_in.cap, c->knobs, ordered_stream(c), c->ev0, c->ev1, in,
+                                    out, items, results, n, rle, dyn, chunk_len, hist_limit, flags,
+                                    c->d_tabs.as<uint32_t>(), &c->last_ms);
+    if (r) return r == -4 ? NDFL_E_DEVICE : NDFL_E_INTERNAL;
     return NDFL_OK;
 }
 

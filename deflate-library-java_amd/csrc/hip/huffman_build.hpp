@@ -1,6 +1,7 @@
 // huffman_build.hpp -- the Huffman codes and header of one DEFLATE block (gfx950), built once for
-// every encoder: the split pipeline's codes kernel runs it on one wave (NT = 64), the one-kernel
-// RLE/LITERAL encoder and the LZ77 encoder on their whole workgroup (NT = 1024).
+// every encoder: the split pipeline's codes kernel and the batched encoder (deflate_batch.hip, with an
+// opaque lane index: OPQ below) run it on one wave (NT = 64), the one-kernel RLE/LITERAL encoder and
+// the LZ77 encoder on their whole workgroup (NT = 1024).
 //
 // Restates D/comp/Lz77Huffman.java:134-265 (trims, single-distance fix-up, package-merge lengths,
 // canonical codes, code-length RLE, code-length code, header) and :309-410 (package-merge, canonical
@@ -80,10 +81,23 @@ struct HuffScr {
     uint8_t clLen[32];
 };
 
+// The thread index of a builder function.  OPQ (one wave only): taken afresh as a value the compiler
+// knows nothing about (opaque_lane, ndfl_common.hpp), for a kernel that builds inside a loop over
+// streams (deflate_batch.hip): the builder's lane masks are then not hoisted out of that loop.
+template <bool OPQ>
+__device__ __forceinline__ int builder_tid() {
+    if constexpr (OPQ) return opaque_lane();
+    else return threadIdx.x;
+}
+
 // Exclusive sum / exclusive suffix minimum over the NT threads: in the wave, or through S.scan().
-template <int NT>
+template <int NT, bool OPQ = false>
 __device__ __forceinline__ uint32_t excl_scan(uint32_t v, HuffScr& S, uint32_t& total) {
-    if constexpr (NT == 64) {
+    if constexpr (NT == 64 && OPQ) {
+        const uint32_t incl = wave_incl_scan_l(v, opaque_lane());
+        total = (uint32_t)__builtin_amdgcn_readlane(incl, 63);
+        return incl - v;
+    } else if constexpr (NT == 64) {
         const uint32_t incl = wave_incl_scan(v);
         total = __shfl(incl, 63, 64);
         return incl - v;
@@ -91,18 +105,19 @@ __device__ __forceinline__ uint32_t excl_scan(uint32_t v, HuffScr& S, uint32_t& 
         return block_excl_scan<uint32_t, NT / 64>(v, S.scan(), total);
     }
 }
-template <int NT>
+template <int NT, bool OPQ = false>
 __device__ __forceinline__ uint32_t excl_suffix_min(uint32_t v, HuffScr& S) {
-    if constexpr (NT == 64) return wave_excl_suffix_min(v, 0xFFFFFFFFu);
+    if constexpr (NT == 64 && OPQ) return wave_excl_suffix_min_l(v, 0xFFFFFFFFu, opaque_lane());
+    else if constexpr (NT == 64) return wave_excl_suffix_min(v, 0xFFFFFFFFu);
     else return block_excl_suffix_min<NT / 64>(v, 0xFFFFFFFFu, S.scan());
 }
 
 // Length-limited code lengths by package-merge (D/comp/Lz77Huffman.java:309-335): merge-path
 // levels, tie order packages before leaves on equal frequency, prefix backtrack.  Thread t takes
 // every NT-th item.  hist: n entries; lens[0..n) receives the lengths.
-template <int NT>
+template <int NT, bool OPQ = false>
 __device__ void pm_lengths(const uint32_t* hist, int n, int L, uint8_t* lens, HuffScr& S) {
-    const int tid = threadIdx.x, lane = tid & 63;
+    const int tid = builder_tid<OPQ>(), lane = tid & 63;
     // the used symbols' keys (freq << 9 | symbol) compacted in symbol order, padded to 4 with ~0
     uint32_t nl = 0;
     for (int base = 0; base < n; base += NT) {                // uniform trip count
@@ -230,9 +245,9 @@ __device__ void pm_lengths(const uint32_t* hist, int n, int L, uint8_t* lens, Hu
 }
 
 // Canonical codes (D/comp/Lz77Huffman.java:368-391): rev(code) | len << 16 into codes[0..n).
-template <int NT>
+template <int NT, bool OPQ = false>
 __device__ void canon_codes(const uint8_t* lens, int n, uint32_t* codes, HuffScr& S) {
-    const int tid = threadIdx.x;
+    const int tid = builder_tid<OPQ>();
     if (tid < 16) S.blc[tid] = 0;
     for (int t = tid; t < 160; t += NT) S.mask[t] = 0;
     __syncthreads();
@@ -268,11 +283,12 @@ __device__ void canon_codes(const uint8_t* lens, int n, uint32_t* codes, HuffScr
 // the code lengths in S.lens with the alphabet sizes in S.misc[0..1], and the complete header
 // (bfinal through the code-length symbols, zero past it) as words in S.hdr().  Returns the header's
 // bits.
-template <int NT>
+template <int NT, bool OPQ = false>
 __device__ __forceinline__ uint32_t build_block_codes(HuffScr& S, bool dynamic, bool is_final, uint32_t* lit_out,
                                                       uint32_t* dist_out) {
     static_assert(NT % 64 == 0 && NT <= 1024, "whole waves, at most the 16 of S.scan()");
-    const int tid = threadIdx.x, lane = tid & 63;
+    static_assert(!OPQ || NT == 64, "the opaque lane index is one wave's");
+    const int tid = builder_tid<OPQ>(), lane = tid & 63;
     if (!dynamic) {
         // fixed codes (:394-410)
         for (int t = tid; t < 288; t += NT) {
@@ -310,11 +326,11 @@ __device__ __forceinline__ uint32_t build_block_codes(HuffScr& S, bool dynamic, 
     __syncthreads();
     const int ln = (int)S.misc[0], dn = (int)S.misc[1];
     const bool emptyDist = S.misc[2] != 0;
-    pm_lengths<NT>(S.hlit, ln, 15, S.lens, S);
+    pm_lengths<NT, OPQ>(S.hlit, ln, 15, S.lens, S);
     if (emptyDist) { if (tid == 0) S.lens[ln] = 0; __syncthreads(); }
-    else pm_lengths<NT>(S.hdist, dn, 15, S.lens + ln, S);
-    canon_codes<NT>(S.lens, ln, lit_out, S);
-    canon_codes<NT>(S.lens + ln, dn, dist_out, S);
+    else pm_lengths<NT, OPQ>(S.hdist, dn, 15, S.lens + ln, S);
+    canon_codes<NT, OPQ>(S.lens, ln, lit_out, S);
+    canon_codes<NT, OPQ>(S.lens + ln, dn, dist_out, S);
     for (int t = ln + tid; t < 288; t += NT) lit_out[t] = 0;
     if (tid >= dn && tid < 32) dist_out[tid] = 0;
     // code-length sequence RLE (:187-223) as maximal-run decomposition; thread t owns [Q t, Q t + Q)
@@ -330,7 +346,7 @@ __device__ __forceinline__ uint32_t build_block_codes(HuffScr& S, bool dynamic, 
         st[q] = i < nc && (i == 0 || S.lens[i - 1] != v[q]);
         if (st[q]) firstStart = (uint32_t)i;
     }
-    uint32_t nxt = min(excl_suffix_min<NT>(firstStart, S), (uint32_t)nc);
+    uint32_t nxt = min(excl_suffix_min<NT, OPQ>(firstStart, S), (uint32_t)nc);
     uint32_t cnt[Q], mycnt = 0;
 #pragma unroll
     for (int q = Q - 1; q >= 0; q--) {
@@ -345,7 +361,7 @@ __device__ __forceinline__ uint32_t build_block_codes(HuffScr& S, bool dynamic, 
         mycnt += cnt[q];
     }
     uint32_t tot;
-    uint32_t k = excl_scan<NT>(mycnt, S, tot);
+    uint32_t k = excl_scan<NT, OPQ>(mycnt, S, tot);
 #pragma unroll
     for (int q = 0; q < Q; q++) {
         if (!st[q]) continue;
@@ -369,8 +385,8 @@ __device__ __forceinline__ uint32_t build_block_codes(HuffScr& S, bool dynamic, 
     __syncthreads();
     for (uint32_t t = (uint32_t)tid; t < tot; t += NT) atomicAdd(&S.clh[S.clSym[t]], 1u);
     __syncthreads();
-    pm_lengths<NT>(S.clh, 19, 7, S.clLen, S);
-    canon_codes<NT>(S.clLen, 19, S.clCode, S);
+    pm_lengths<NT, OPQ>(S.clh, 19, 7, S.clLen, S);
+    canon_codes<NT, OPQ>(S.clLen, 19, S.clCode, S);
     for (int i = tid; i < HDRW; i += NT) S.hdr()[i] = 0;             // (hdr shares pf[0])
     // per-symbol header bit offsets (exclusive scan, thread t owns [Q t, Q t + Q))
     uint32_t sb[Q], lsum = 0;
@@ -385,7 +401,7 @@ __device__ __forceinline__ uint32_t build_block_codes(HuffScr& S, bool dynamic, 
         lsum += sb[q];
     }
     uint32_t body;
-    uint32_t so = excl_scan<NT>(lsum, S, body);
+    uint32_t so = excl_scan<NT, OPQ>(lsum, S, body);
 #pragma unroll
     for (int q = 0; q < Q; q++) {
         const uint32_t i = (uint32_t)(Q * tid + q);

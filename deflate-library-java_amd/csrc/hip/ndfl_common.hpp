@@ -31,8 +31,8 @@ struct Knobs {
     uint32_t flat_min = 49152;   // NDFL_FLAT_MIN: chains to count at least for flat groups (their latency)
     bool test_segflip = false;   // NDFL_TEST_SEGFLIP: one count-pass record's byte count perturbed
                                  //   before the emit pass (the emit-side check must fail the decode)
-    uint32_t batch_waves = 0;    // NDFL_BATCH_WAVES: cap of ndfl_inflate_batch's / _members' grid (0: automatic); the
-                                 //   tests put many streams on one wave with it
+    uint32_t batch_waves = 0;    // NDFL_BATCH_WAVES: cap of ndfl_inflate_batch's / _members' / ndfl_deflate_batch's grid
+                                 //   (0: automatic); the tests put many streams on one wave with it
     void read() {
         auto on = [](const char* n) { const char* e = getenv(n); return e && strcmp(e, "0") != 0; };
         auto num = [](const char* n, int dflt) { const char* e = getenv(n); return e ? atoi(e) : dflt; };
@@ -214,6 +214,42 @@ __device__ __forceinline__ uint32_t wave_excl_suffix_min(uint32_t v, uint32_t id
         if (lane + o < 64) x = min(x, y);
     }
     const uint32_t nxt = __shfl_down(x, 1, 64);
+    return lane == 63 ? ident : nxt;
+}
+
+// The lane index as a value the compiler knows nothing about.  A kernel that runs its wave-wide
+// steps inside a loop over streams takes it afresh inside the loop: masks derived from threadIdx
+// (lane >= 2, lane < 29, ...) are loop-invariant, get hoisted to the kernel's entry and are then held
+// in scalar register pairs across everything -- spilled, once there are dozens of them
+// (deflate_batch.hip; inflate_batch_loop.inc reads its lane index back from LDS for the same reason).
+__device__ __forceinline__ int opaque_lane() {
+    int l = threadIdx.x;
+    asm volatile("" : "+v"(l));
+    return l;
+}
+
+// wave_incl_scan / wave_excl_suffix_min with the lane index given (an opaque_lane()); the value of
+// lane `src` mod 64 by ds_bpermute (__shfl_up / __shfl_down take the lane index from mbcnt and clamp
+// it with compares of their own, which are hoisted the same way).
+__device__ __forceinline__ uint32_t lane_value(uint32_t x, int src) {
+    return (uint32_t)__builtin_amdgcn_ds_bpermute(src << 2, (int)x);
+}
+__device__ __forceinline__ uint32_t wave_incl_scan_l(uint32_t x, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t y = lane_value(x, lane - o);
+        if (lane >= o) x += y;
+    }
+    return x;
+}
+__device__ __forceinline__ uint32_t wave_excl_suffix_min_l(uint32_t v, uint32_t ident, int lane) {
+    uint32_t x = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t y = lane_value(x, lane + o);
+        if (lane + o < 64) x = min(x, y);
+    }
+    const uint32_t nxt = lane_value(x, lane + 1);
     return lane == 63 ? ident : nxt;
 }
 

@@ -448,6 +448,80 @@ class Context:
             todo = again
         return done
 
+    def deflate_batch_raw(self, in_addr, in_size, out_addr, out_size, items, strategy, chunk_len, hist_limit, flags):
+        """ndfl_deflate_batch: `items` is a sequence of (in_off, in_len, out_off, out_cap, format, sum):
+        item i's raw bytes, the region of its compressed member, its container (FMT_*) and, for FMT_RAW,
+        the checksum wanted (SUM_*).  Returns one (status, checksum, out_len, end_bits) per stream; status
+        = 0 / E_CAPACITY."""
+        L = load()
+        self._order()
+        n = len(items)
+        arr = (_lib.MemberItem * max(1, n))(*[_lib.MemberItem(*map(int, it)) for it in items])
+        res = (_lib.DeflateResult * max(1, n))()
+        sid = _strategy_id(strategy)
+        if not isinstance(sid, int):                 # (strategy objects: only the presets are batched)
+            raise NdflError(_lib.E_UNSUPPORTED, "ndfl_deflate_batch")
+        check(L.ndfl_deflate_batch(self._h, in_addr, in_size, out_addr, out_size, arr, res, n, sid,
+                                   chunk_len, hist_limit, flags), "ndfl_deflate_batch")
+        return [(r.status, r.checksum, r.out_len, r.end_bits) for r in res[:n]]
+
+    def _deflate_packed(self, buffers, fmt, kind, headers, strategy, chunk_len, hist_limit):
+        """One batch over host buffers: each region is its header's bytes (the caller's part of a
+        container) followed by room for ndfl_deflate_bound(len) bytes and the trailer.  Returns one
+        (bytes from the header on, end_bits, checksum) per buffer."""
+        L = load()
+        buffers = [bytes(b) for b in buffers]
+        packed = b"".join(buffers)
+        src = ctypes.create_string_buffer(packed, max(1, len(packed)))
+        items, regions, in_off, out_off = [], [], 0, 0
+        for b, h in zip(buffers, headers):
+            cap = L.ndfl_deflate_bound(len(b), chunk_len) + 8
+            items.append((in_off, len(b), out_off + len(h), cap, fmt, kind))
+            regions.append(out_off)
+            in_off += len(b)
+            out_off += len(h) + cap
+        out = ctypes.create_string_buffer(max(1, out_off))
+        for at, h in zip(regions, headers):
+            ctypes.memmove(ctypes.addressof(out) + at, bytes(h), len(h))
+        res = self.deflate_batch_raw(ctypes.addressof(src), len(packed), ctypes.addressof(out), out_off, items,
+                                     strategy, chunk_len, hist_limit, 0)
+        done = []
+        for at, h, r in zip(regions, headers, res):
+            status, checksum, olen, end_bits = r
+            check(status, "ndfl_deflate_batch")
+            done.append((ctypes.string_at(ctypes.addressof(out) + at, len(h) + olen), end_bits, checksum))
+        return done
+
+    def deflate_batch(self, buffers, strategy=Strategy.RLE_DYNAMIC, chunk_len=65536, hist_limit=32768, sum=None):
+        """Compress many independent host buffers in one call, each as deflate() compresses it alone
+        (RLE_* / LITERAL_* presets).  Returns one (bytes, end_bits, checksum) per buffer; checksum is
+        the buffer's CRC-32 / Adler-32 with sum = SUM_CRC32 / SUM_ADLER32, else 0."""
+        buffers = list(buffers)
+        kind = _lib.SUM_NONE if sum is None else int(sum)
+        return self._deflate_packed(buffers, _lib.FMT_RAW, kind, [b""] * len(buffers), strategy, chunk_len, hist_limit)
+
+    def deflate_members(self, buffers, format, meta=None, strategy=Strategy.RLE_DYNAMIC, chunk_len=65536,
+                        hist_limit=32768):
+        """Compress many independent host buffers into complete zlib (FMT_ZLIB) or gzip (FMT_GZIP)
+        members in one call: what ZlibOutputStream / GzipOutputStream write for each buffer alone.  The
+        header is `meta`'s (a ZlibMetadata / GzipMetadata; default ZlibMetadata.DEFAULT / GzipMetadata()),
+        the trailer the kernel's.  Returns one bytes object per buffer."""
+        from .streams import GzipMetadata, ZlibMetadata
+        buffers = list(buffers)
+        fmt = int(format)
+        if fmt == _lib.FMT_ZLIB:
+            header = bytes((meta if meta is not None else ZlibMetadata.DEFAULT).header_bytes())
+        elif fmt == _lib.FMT_GZIP:
+            meta = meta if meta is not None else GzipMetadata()
+            header = bytes(meta.header_bytes())
+            if meta.hasHeaderCrc:
+                header += (self.crc32(header) & 0xFFFF).to_bytes(2, "little")
+        else:
+            raise ValueError("format: FMT_ZLIB or FMT_GZIP")
+        done = self._deflate_packed(buffers, fmt, _lib.SUM_NONE, [header] * len(buffers), strategy, chunk_len,
+                                    hist_limit)
+        return [d[0] for d in done]
+
     def inflate_range_raw(self, in_addr, in_len, start_bit, end_bit, out_addr, dict_len, out_cap, flags):
         """ndfl_inflate_range: decode bits [start_bit, end_bit) into out_addr + dict_len, with the
         dict_len bytes at out_addr as the window.  Returns (code, out_len, consumed_bits)."""

@@ -40,7 +40,7 @@ EXPORTS = ["ndfl_abi_version", "ndfl_error_string", "ndfl_ctx_create", "ndfl_ctx
            "ndfl_inflate", "ndfl_inflate_range", "ndfl_inflate_resolve", "ndfl_bits_shift", "ndfl_crc32", "ndfl_adler32",
            "ndfl_crc32_combine", "ndfl_decide", "ndfl_compress_to", "ndfl_decision_free", "ndfl_inflate_sync",
            "ndfl_inflate_tail", "ndfl_inflate_headers", "ndfl_inflate_tail_map", "ndfl_ctx_error_symbol",
-           "ndfl_inflate_batch", "ndfl_inflate_members"]
+           "ndfl_inflate_batch", "ndfl_inflate_members", "ndfl_deflate_batch"]
 
 # ndfl_inflate_members: NDFL_FMT_* (an item's container) and NDFL_SUM_* (a raw item's checksum)
 FMT_RAW, FMT_ZLIB, FMT_GZIP = 0, 1, 2
@@ -91,6 +91,12 @@ class MemberResult(ctypes.Structure):
                 ("checksum", ctypes.c_uint32), ("header_len", ctypes.c_uint32)]
 
 
+class DeflateResult(ctypes.Structure):
+    """ndfl_deflate_result (include/ndfl.h)."""
+    _fields_ = [("status", ctypes.c_int32), ("checksum", ctypes.c_uint32),
+                ("out_len", ctypes.c_uint64), ("end_bits", ctypes.c_uint64)]
+
+
 _lib = None
 
 
@@ -133,6 +139,11 @@ def load():
     if hasattr(L, "ndfl_inflate_members"):
         L.ndfl_inflate_members.argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(MemberItem),
                                            ctypes.POINTER(MemberResult), u32, u32]
+    # (and the batched deflate: scripts/bench_batch.py --mode deflate-loop measures its baseline on the
+    # build before it)
+    if hasattr(L, "ndfl_deflate_batch"):
+        L.ndfl_deflate_batch.argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(MemberItem),
+                                         ctypes.POINTER(DeflateResult), u32, i32, u32, u32, u32]
     L.ndfl_inflate_range.argtypes = [vp, vp, u64, u64, u64, vp, u64, u64, ctypes.POINTER(u64), ctypes.POINTER(u64),
                                      u32]
     L.ndfl_inflate_resolve.argtypes = [vp, ctypes.POINTER(u64)]

@@ -341,6 +341,65 @@ int ndfl_inflate_members(ndfl_ctx* ctx, const uint8_t* in, uint64_t in_size, uin
                          const ndfl_member_item* items, ndfl_member_result* results, uint32_t n, uint32_t flags);
 
 /*
+ * Compress n independent buffers in one call: one kernel launch and one host sync whatever n is
+ * (ndfl_deflate_chunks costs about eight launches and a sync per buffer).  The encoder's counterpart of
+ * ndfl_inflate_batch / ndfl_inflate_members, with their items read the other way round: item i's raw
+ * bytes are in[in_off, in_off + in_len), its compressed member goes to out[out_off, out_off + out_cap).
+ * Stream i is exactly DeflaterOutputStream(out, chunk_len, hist_limit, strategy): write all bytes, then
+ * finish() (D/DeflaterOutputStream.java:119-171).  Its DEFLATE bytes are bit-identical to
+ * ndfl_deflate_chunks(ctx, NULL, 0, hist_limit, data_i, len_i, chunk_len, strategy, 1, 0, ...): the
+ * stream starts at bit 0 of out[out_off], the unused high bits of its last DEFLATE byte are 0, an empty
+ * buffer gives the one empty final block, and a stream never sees a neighbour's bytes (chunk 0 has no
+ * history; a later chunk has its own stream's previous byte, and only when hist_limit > 0).  One wave
+ * encodes a stream, chunk by chunk: the call is for MANY SMALL buffers (per-record zlib bodies, PNG IDAT
+ * payloads, zip entries, small gzip members).
+ *   strategy    NDFL_LITERAL_STATIC, NDFL_LITERAL_DYNAMIC, NDFL_RLE_STATIC or NDFL_RLE_DYNAMIC.
+ *               NDFL_FULL_* and NDFL_UNCOMPRESSED return NDFL_E_UNSUPPORTED for the call and nothing is
+ *               written (the LZ77 match search takes one history start per call; not batched).
+ *   chunk_len   1..65536 (0: NDFL_E_ARG; above 65536: NDFL_E_UNSUPPORTED, as ndfl_deflate_chunks)
+ *   hist_limit  0..32768, else NDFL_E_ARG
+ *   format      NDFL_FMT_*.  A container's header does not depend on the data and is the caller's, written
+ *               in front of out_off before or after the call; the trailer does, and the kernel appends it
+ *               after the byte-aligned DEFLATE data:
+ *                 NDFL_FMT_RAW   no trailer; checksum = the java.util.zip CRC-32 (initial 0) or Adler-32
+ *                                (initial 1) of the input bytes as `sum` asks, 0 with NDFL_SUM_NONE
+ *                 NDFL_FMT_ZLIB  4 bytes: the big-endian Adler-32 of the input (D/ZlibOutputStream.java);
+ *                                checksum = the Adler-32; `sum` is not read
+ *                 NDFL_FMT_GZIP  8 bytes: the CRC-32, then (uint32_t)in_len, both little-endian
+ *                                (D/GzipOutputStream.java); checksum = the CRC-32; `sum` is not read
+ *               The checksum is taken from the bytes on their way through the encoder, in the same launch.
+ *   results     host memory, one per stream.  out_len = ceil(end_bits / 8) + the trailer's bytes.  A
+ *               member longer than out_cap has status NDFL_E_CAPACITY and out_len = the bytes required;
+ *               its first out_cap bytes are stored, and the other streams are unaffected.
+ * No byte of `out` outside [out_off, out_off + min(out_len, out_cap)) of some stream is written, whatever
+ * the statuses, at any byte alignment of `out` and out_off, with regions that touch: a stream's first
+ * and last partial words go out as byte stores.
+ * Buffers, NDFL_IN_DEVICE / NDFL_OUT_DEVICE (host buffers are staged through the context), stream
+ * ordering and ndfl_ctx_last_kernel_ms as for ndfl_inflate_batch.  Input regions may overlap or repeat;
+ * output regions must not overlap.
+ * Returns 0 when the batch ran (n == 0 returns 0 and touches nothing); NDFL_E_ARG, with nothing encoded,
+ * for null pointers with n > 0, an item outside in_size / out_size, overlapping output regions, or an
+ * item's format > 2 or sum > 2; NDFL_E_DEVICE on HIP errors.
+ * Crossover to ndfl_deflate_chunks (measured on one MI355X, RLE_DYNAMIC with a CRC-32, DESIGN.md §4 "Batched
+ * deflate"): a loop of ndfl_deflate_chunks calls costs 0.16 to 0.27 ms per buffer up to 1 MiB, nearly all of it
+ * per-call cost; the batch costs about 0.1 ms per call, a wave about 0.1 ms per stream plus 24 us per KiB (41 MB/s),
+ * and up to 3,072 waves run at once.  65,536 x 512 B take 2.7 to 2.9 ms in a batch and 10.6 to 12.0 s in a loop,
+ * 4,096 x 4 KiB 0.50 to 0.55 ms and 661 to 871 ms, 256 x 1 MiB 25 to 28 ms and 48 to 69 ms.  So one buffer alone
+ * goes through ndfl_deflate_chunks; two buffers are faster in a batch below about 5 KB each, ten below about
+ * 57 KB, a hundred below about 650 KB, 256 below about 1.7 MB.  A buffer of many MiB, which ndfl_deflate_chunks
+ * encodes at tens of GB/s by working inside the stream, belongs there whatever the count.
+ */
+typedef struct {
+    int32_t  status;             /* 0 or NDFL_E_CAPACITY */
+    uint32_t checksum;           /* see above */
+    uint64_t out_len;            /* bytes of the member; with NDFL_E_CAPACITY: bytes required */
+    uint64_t end_bits;           /* DEFLATE bits written, from the stream's own bit 0 */
+} ndfl_deflate_result;           /* 24 bytes */
+int ndfl_deflate_batch(ndfl_ctx* ctx, const uint8_t* in, uint64_t in_size, uint8_t* out, uint64_t out_size,
+                       const ndfl_member_item* items, ndfl_deflate_result* results, uint32_t n,
+                       int strategy, uint32_t chunk_len, uint32_t hist_limit, uint32_t flags);
+
+/*
  * Decompress the block-aligned bit range [start_bit, end_bit) of one raw DEFLATE stream: one GPU's
  * shard of a stream decoded across GPUs, or one batch of a stream read incrementally
  * (NDFL_IN_PARTIAL, end_bit UINT64_MAX: InflaterInputStream's bounded input buffer,

@@ -21,6 +21,10 @@ output byte against the original data.
 --mode loop needs only ndfl_inflate, so it also runs on a build without the batch entry point
 (NDFL_LIB_PATH selects the library): that is the baseline.  Likewise --mode batch+sum runs on a build
 without ndfl_inflate_members.
+
+The encoder's side (--mode deflate | deflate-loop, --data text | runs; see deflate_modes): one
+ndfl_deflate_batch call against one ndfl_deflate_chunks call per buffer, RLE_DYNAMIC with the CRC-32
+of each buffer, on the same three shapes; the lines are "bench": "batch_deflate".
 """
 import argparse
 import ctypes
@@ -67,9 +71,122 @@ def wrap(fmt, raw, data):
     return raw, 0, c
 
 
+def make_buffers(name, seed, kind):
+    """The raw buffers of the deflate modes: make_streams' word-salad text ("text"), or that text with
+    runs of 4..47 equal bytes spliced in between pieces of 8..63 bytes ("runs": RLE has something to do)."""
+    import numpy as np
+    n, size = SHAPES[name]
+    rng = random.Random(seed)
+    words = [rng.randbytes(rng.randrange(2, 9)) for _ in range(200)]
+    rs = np.random.RandomState(seed)
+    datas = []
+    for _ in range(n):
+        idx = rs.randint(0, 200, size // 4 + 1)
+        data = b"".join(map(words.__getitem__, idx))[:size]
+        if kind == "runs":
+            # segments alternate: 8..63 bytes of the text as it is, then 4..47 bytes overwritten with one value
+            m = size // 12 + 2
+            seg = np.empty(2 * m, dtype=np.int64)
+            seg[0::2] = rs.randint(8, 64, m)
+            seg[1::2] = rs.randint(4, 48, m)
+            vals = rs.randint(0, 256, m).astype(np.uint8)
+            which = np.repeat(np.arange(2 * m), seg)[:size]
+            text = np.frombuffer(data, dtype=np.uint8)
+            data = np.where(which & 1, vals[which >> 1], text).astype(np.uint8).tobytes()
+        assert len(data) == size
+        datas.append(data)
+    return datas
+
+
+def deflate_modes(a, modes):
+    """--mode deflate: one ndfl_deflate_batch call (raw DEFLATE with the CRC-32 of each buffer);
+    --mode deflate-loop: one ndfl_deflate_chunks call per buffer with crc_inout, which also runs on a
+    build without the batch entry point (NDFL_LIB_PATH): the baseline.  Input and output are
+    device-resident; every buffer and every output region starts 16-byte aligned, and a region holds
+    ndfl_deflate_bound bytes, so the loop's encoder writes it in place.  The first pass decodes every
+    region with ndfl_inflate_members (raw + CRC-32) and compares the bytes and the checksums."""
+    import torch
+    import ndfl
+    ctx = ndfl.Context(0)
+    ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+    L = ndfl._lib.load()
+    flags = ndfl.IN_DEVICE | ndfl.OUT_DEVICE
+    strategy = ndfl._lib.STRATEGIES["RLE_DYNAMIC"]
+    chunk_len, hist_limit = 65536, 32768
+    u64, u32 = ctypes.c_uint64, ctypes.c_uint32
+    for name in a.shapes.split(","):
+        n, size = SHAPES[name]
+        datas = make_buffers(name, a.seed, a.data)
+        want = b"".join(datas)
+        crcs = [zlib.crc32(d) for d in datas]
+        in_stride = (size + 15) // 16 * 16
+        cap = (L.ndfl_deflate_bound(size, chunk_len) + 16 + 15) // 16 * 16
+        host = bytearray(n * in_stride)
+        for i, d in enumerate(datas):
+            host[i * in_stride:i * in_stride + size] = d
+        d_in = torch.frombuffer(host, dtype=torch.uint8).cuda()
+        d_out = torch.zeros(n * cap, dtype=torch.uint8, device="cuda")
+        d_back = torch.zeros(n * size, dtype=torch.uint8, device="cuda")
+        pi, po = d_in.data_ptr(), d_out.data_ptr()
+        for mode in modes:
+            out_lens, sums = [0] * n, [0] * n
+            if mode == "deflate":
+                arr = (ndfl._lib.MemberItem * n)(*[ndfl._lib.MemberItem(i * in_stride, size, i * cap, cap, ndfl._lib.FMT_RAW,
+                                                                        ndfl._lib.SUM_CRC32) for i in range(n)])
+                res = (ndfl._lib.DeflateResult * n)()
+
+            def once():
+                if mode == "deflate":
+                    rc = L.ndfl_deflate_batch(ctx._h, pi, n * in_stride, po, n * cap, arr, res, n, strategy, chunk_len,
+                                              hist_limit, flags)
+                    assert rc == 0, rc
+                    return ctx.last_kernel_ms()
+                bits, crc = u64(0), u32(0)
+                for i in range(n):
+                    crc.value = 0
+                    rc = L.ndfl_deflate_chunks(ctx._h, None, 0, hist_limit, pi + i * in_stride, size, chunk_len, strategy, 1,
+                                               0, po + i * cap, cap, ctypes.byref(bits), ctypes.byref(crc), flags)
+                    assert rc == 0, rc
+                    out_lens[i] = (bits.value + 7) // 8
+                    sums[i] = crc.value
+                return None
+
+            times, kms = [], None
+            for it in range(a.warmup + a.reps):
+                d_out.zero_()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                kms = once()
+                torch.cuda.synchronize()
+                dt = (time.perf_counter() - t0) * 1e3
+                if it == 0:
+                    if mode == "deflate":
+                        assert all(r.status == 0 for r in res)
+                        out_lens, sums = [r.out_len for r in res], [r.checksum for r in res]
+                    assert sums == crcs, "checksums differ"
+                    back = ctx.inflate_members_raw(po, n * cap, d_back.data_ptr(), n * size,
+                                                   [(i * cap, out_lens[i], i * size, size, ndfl._lib.FMT_RAW,
+                                                     ndfl._lib.SUM_CRC32) for i in range(n)], flags)
+                    assert all(r[0] == 0 and r[2] == size and r[4] == c for r, c in zip(back, crcs)), "round trip"
+                    assert bytes(d_back.cpu().numpy()) == want, "round trip: bytes differ"
+                if it >= a.warmup:
+                    times.append(dt)
+            med = statistics.median(times)
+            line = {"bench": "batch_deflate", "label": a.label, "mode": mode, "data": a.data, "shape": name, "buffers": n,
+                    "buffer_bytes": size, "in_bytes": n * size, "out_bytes": sum(out_lens), "strategy": "RLE_DYNAMIC",
+                    "ms_median": round(med, 3), "ms_all": [round(t, 3) for t in times],
+                    "in_MBps": round(n * size / med / 1e3, 1)}
+            if kms is not None:
+                line["kernel_ms_last"] = round(kms, 3)
+            print(json.dumps(line), flush=True)
+        del d_in, d_out, d_back
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", required=True, help="comma-separated: loop, batch, members, batch+sum")
+    ap.add_argument("--mode", required=True,
+                    help="comma-separated: loop, batch, members, batch+sum; or deflate, deflate-loop")
+    ap.add_argument("--data", choices=["text", "runs"], default="text", help="deflate modes: the buffers' content")
     ap.add_argument("--format", choices=["zlib", "gzip", "raw-crc"], default="zlib",
                     help="members / batch+sum: the container of each stream")
     ap.add_argument("--shapes", default=",".join(SHAPES))
@@ -78,6 +195,8 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--label", default="")
     a = ap.parse_args()
+    if all(m in ("deflate", "deflate-loop") for m in a.mode.split(",")):
+        return deflate_modes(a, a.mode.split(","))
     import torch
     import ndfl
     ctx = ndfl.Context(0)

@@ -1,0 +1,451 @@
+"""ndfl_deflate_batch on the GPU: many independent buffers compressed in one call, each stream
+checked against the CPU oracle on that buffer alone -- the DEFLATE bytes are O.deflate(buffer, strategy,
+chunk_len, hist_limit), end_bits is O.deflate_chunks(b"", buffer, True, ...)'s, the checksums are
+Python's zlib.crc32 / zlib.adler32 -- and every byte of `out` outside the streams' stored bytes must
+still hold the fill byte.
+
+The buffers are the places where the batch kernel (csrc/hip/deflate_batch.hip) can go wrong: a wave
+walks a chunk in steps of 64 lanes x 16 bytes and carries the run piece that is open at a step's end
+into the next step, so runs start and end around every boundary it has (16 bytes per lane, 1024 bytes
+per step, the chunk length), at the run lengths where the closed-form parse changes shape (remainders
+0..3 after whole 258s, with and without the lead literal).
+"""
+import concurrent.futures
+import ctypes
+import functools
+import gzip
+import random
+import struct
+import zlib
+
+import pytest
+
+import adversarial_hist as A
+import knobs
+import oracle_lib as O
+
+pytestmark = pytest.mark.gpu
+
+FILL = 0xA5
+E_ARG, E_UNSUPPORTED, E_CAPACITY = -1, -2, -3
+RAW, ZLIB, GZIP = 0, 1, 2
+NONE, CRC32, ADLER32 = 0, 1, 2
+STRATEGIES = ["LITERAL_STATIC", "LITERAL_DYNAMIC", "RLE_STATIC", "RLE_DYNAMIC"]
+CONFIGS = [(65536, 32768), (259, 32768), (259, 0), (7, 32768), (1, 32768)]
+BPL, STEP = 16, 1024              # the kernel's bytes per lane and per step (deflate_batch.hip)
+BIG = 65535                       # buffers from this size on run at chunk_len 65536 only
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    import torch
+    import ndfl
+    c = ndfl.Context(0)
+    c.set_stream(torch.cuda.current_stream().cuda_stream)     # ordered with torch's kernels
+    return c
+
+
+@pytest.fixture(scope="module")
+def one_wave():
+    import torch
+    c = knobs.context(NDFL_BATCH_WAVES=1)
+    c.set_stream(torch.cuda.current_stream().cuda_stream)
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def oracle(buf, strategy="RLE_DYNAMIC", chunk_len=65536, hist_limit=32768):
+    """(DEFLATE bytes, end bits) of one buffer alone, computed once."""
+    comp = O.deflate(buf, strategy, chunk_len, hist_limit)
+    comp2, bits = O.deflate_chunks(b"", buf, True, strategy, chunk_len, hist_limit)
+    assert comp2 == comp and (bits + 7) // 8 == len(comp)
+    return comp, bits
+
+
+def trailer(buf, fmt):
+    if fmt == ZLIB:
+        return struct.pack(">I", zlib.adler32(buf))
+    if fmt == GZIP:
+        return struct.pack("<II", zlib.crc32(buf), len(buf) & 0xFFFFFFFF)
+    return b""
+
+
+def checksum(buf, fmt, kind):
+    kind = ADLER32 if fmt == ZLIB else CRC32 if fmt == GZIP else kind
+    return {NONE: 0, CRC32: zlib.crc32(buf), ADLER32: zlib.adler32(buf)}[kind]
+
+
+def member(buf, fmt, cfg):
+    """(the member's bytes as the kernel writes them, end bits)."""
+    comp, bits = oracle(buf, *cfg)
+    return comp + trailer(buf, fmt), bits
+
+
+def pack_inputs(items):
+    """The items' buffers back to back (no gaps): (packed, [in_off])."""
+    packed, offs = bytearray(), []
+    for buf, _, _ in items:
+        offs.append(len(packed))
+        packed += buf
+    return bytes(packed), offs
+
+
+def run(ctx, items, cfg, regions=None, caps=None, out_size=None, out_shift=0, inputs=None):
+    """One ndfl_deflate_batch call on host buffers.  items: (buffer, format, sum); cfg: (strategy,
+    chunk_len, hist_limit); regions: (out_off, out_cap) per item, default consecutive regions of caps[i]
+    (default: the member's length) bytes, so that all regions touch.  `out` is pre-filled with FILL and
+    starts out_shift bytes into its allocation.  inputs: (packed, [in_off]) instead of the items' buffers
+    back to back.  Returns (results, out bytes, regions)."""
+    if regions is None:
+        regions, off = [], 0
+        for i, (buf, fmt, _) in enumerate(items):
+            cap = caps[i] if caps is not None else len(member(buf, fmt, cfg)[0])
+            regions.append((off, cap))
+            off += cap
+    if out_size is None:
+        out_size = max([o + c for o, c in regions] + [1])
+    packed, offs = inputs if inputs is not None else pack_inputs(items)
+    recs = [(io, len(buf), o, c, fmt, kind) for (buf, fmt, kind), io, (o, c) in zip(items, offs, regions)]
+    src = ctypes.create_string_buffer(packed, max(1, len(packed)))
+    out = ctypes.create_string_buffer(bytes([FILL]) * (out_size + out_shift), out_size + out_shift)
+    res = ctx.deflate_batch_raw(ctypes.addressof(src), len(packed), ctypes.addressof(out) + out_shift, out_size, recs,
+                                *cfg, 0)
+    assert out.raw[:out_shift] == bytes([FILL]) * out_shift
+    return res, out.raw[out_shift:], regions
+
+
+def check(items, cfg, res, out, regions, what=""):
+    """Every stream against the oracle (the first min(out_len, cap) bytes are stored), the zero high
+    bits of its last DEFLATE byte, and every other byte of `out` still FILL."""
+    expect = bytearray(bytes([FILL]) * len(out))
+    for i, ((buf, fmt, kind), r, (off, cap)) in enumerate(zip(items, res, regions)):
+        exp, bits = member(buf, fmt, cfg)
+        status, ck, olen, end_bits = r
+        where = (what, cfg, i, len(buf), off, cap)
+        assert status == (E_CAPACITY if len(exp) > cap else 0), (where, status)
+        assert olen == len(exp), (where, olen, len(exp))
+        assert end_bits == bits, (where, end_bits, bits)
+        assert ck == checksum(buf, fmt, kind), (where, ck)
+        last = exp[(bits + 7) // 8 - 1]
+        assert bits % 8 == 0 or last >> (bits % 8) == 0, where
+        n = min(len(exp), cap)
+        expect[off:off + n] = exp[:n]
+    if out != bytes(expect):
+        bad = next(k for k in range(len(out)) if out[k] != expect[k])
+        owner = [i for i, (off, cap) in enumerate(regions) if off <= bad < off + cap]
+        raise AssertionError((what, cfg, "first wrong byte", bad, "region of stream", owner,
+                              [len(items[i][0]) for i in owner], out[bad], expect[bad]))
+
+
+def run_check(ctx, items, cfg, what="", **kw):
+    res, out, regions = run(ctx, items, cfg, **kw)
+    check(items, cfg, res, out, regions, what)
+    return res
+
+
+def salad(rng, n):
+    words = [rng.randbytes(rng.randrange(2, 9)) for _ in range(200)]
+    return b"".join(rng.choice(words) for _ in range(n // 4 + 1))[:n]
+
+
+def no_runs(rng, n):
+    """n random bytes with no two equal neighbours, so that the only runs are the ones spliced in."""
+    b = bytearray(rng.randbytes(n))
+    for i in range(1, n):
+        if b[i] == b[i - 1]:
+            b[i] = (b[i] + 1 + (i + 1 < n and b[i + 1] == (b[i] + 1) & 0xFF)) & 0xFF
+    return b
+
+
+def with_run(rng, n, start, length):
+    """no_runs bytes with bytes [start, start + length) one value that differs from both neighbours."""
+    b = no_runs(rng, n)
+    v = next(x for x in range(256) if x != b[start - 1 if start else 0] and (start + length >= n or x != b[start + length]))
+    b[start:start + length] = bytes([v]) * length
+    return bytes(b)
+
+
+def mixed(rng, n):
+    """Runs and text, with a run across every 64 KiB boundary."""
+    b = bytearray()
+    while len(b) < n:
+        b += bytes([rng.randrange(4)]) * rng.randrange(1, 700) + salad(rng, rng.randrange(0, 400))
+    b = b[:n]
+    for k in range(65536, n, 65536):
+        b[k - 300:min(n, k + 300)] = b"\x07" * (min(n, k + 300) - (k - 300))
+    return bytes(b)
+
+
+BOUNDARIES = [7, BPL, 2 * BPL, 259, 2 * 259, STEP, 2 * STEP, 65536]
+
+
+@functools.lru_cache(maxsize=None)
+def parity_buffers():
+    rng = random.Random(0xDEF1A7E)
+    bufs = [b"", b"a", b"ab", b"aa", b"abc", b"aaa"]
+    bufs += [b"\x55" * n for n in (3, 4, 257, 258, 259, 260, 261, 262, 516, 517, 519, 776, 4097)]
+    for B in BOUNDARIES:
+        pad = 700 if B < BIG else 40
+        for d in range(-3, 4):
+            for length in (4, 300 if B < BIG else 30):
+                if B + d >= 0:
+                    bufs.append(with_run(rng, B + pad, B + d, length))                      # starts at B + d
+                if B + d - length >= 0:
+                    bufs.append(with_run(rng, B + pad, B + d - length, length))             # ends at B + d
+        bufs.append(with_run(rng, B + pad, max(0, B - 150), 300))                            # straddles B
+        bufs += [bytes(no_runs(rng, n)) for n in (B - 1, B, B + 1)]
+        bufs += [b"\x00" * n for n in (B - 1, B, B + 1)]
+    bufs.append(b"ab" * 1500)
+    bufs.append(rng.randbytes(5000))
+    bufs.append(bytes(range(256)))
+    bufs.append(salad(rng, 6000))
+    # (the 15-bit literal/length limit and the 7-bit code-length limit: test_oracle_deflate.py asserts that
+    # these inputs reach them on the oracle's streams)
+    bufs += [c.data for cls in ("lit_limit", "cl_limit") for c in A.cases(cls)]
+    bufs += [mixed(rng, n) for n in (65535, 65536, 65537, 131073)]
+    return bufs
+
+
+@pytest.mark.parametrize("chunk_len,hist_limit", CONFIGS)
+@pytest.mark.parametrize("strategy", STRATEGIES)
+def test_parity(ctx, strategy, chunk_len, hist_limit):
+    bufs = [b for b in parity_buffers() if chunk_len == 65536 or len(b) < BIG]
+    assert len(bufs) > 200
+    cfg = (strategy, chunk_len, hist_limit)
+    # the oracle's streams, eight buffers at a time (or_deflate keeps no state between calls once its
+    # fixed-code tables exist, and ctypes releases the interpreter lock): chunk_len 1 is 500,000 blocks
+    oracle(b"", *cfg)
+    with concurrent.futures.ThreadPoolExecutor(8) as pool:
+        list(pool.map(lambda b: oracle(b, *cfg), bufs))
+    res = run_check(ctx, [(b, RAW, NONE) for b in bufs], cfg, "parity")
+    assert all(r[0] == 0 for r in res)
+
+
+LAYOUT_LENGTHS = [0, 1, 2, 3, 5, 15, 16, 17, 40, 258, 700, 1023, 1024, 1025, 3000, 5000]
+
+
+def layout_items():
+    rng = random.Random(77)
+    items = []
+    for k, n in enumerate(LAYOUT_LENGTHS * 2):
+        buf = mixed(rng, n) if k % 2 else salad(rng, n)
+        items.append((buf, (RAW, ZLIB, GZIP)[k % 3], (NONE, CRC32, ADLER32)[k % 3]))
+    return items
+
+
+def test_layout_touching_regions_every_residue(ctx):
+    """Regions that touch, with out_off at every residue mod 16 (the members' lengths shift them, and a
+    leading pad of 0..15 bytes shifts all of them), and `out` itself at an odd address."""
+    cfg = ("RLE_DYNAMIC", 65536, 32768)
+    items = layout_items()
+    seen = set()
+    for pad in range(16):
+        regions, off = [], pad
+        for buf, fmt, _ in items:
+            n = len(member(buf, fmt, cfg)[0])
+            regions.append((off, n))
+            seen.add(off % 16)
+            off += n
+        res, out, _ = run(ctx, items, cfg, regions=regions, out_size=off + 5, out_shift=1 if pad % 2 else 0)
+        check(items, cfg, res, out, regions, f"pad {pad}")
+    assert seen == set(range(16))
+
+
+def test_layout_shuffled_regions_with_gaps_and_shared_inputs(ctx):
+    """Regions in an order other than the item order, with gaps of 0..9 bytes; one input region used by
+    two items and overlapped by a third."""
+    cfg = ("RLE_DYNAMIC", 259, 32768)
+    rng = random.Random(5)
+    items = layout_items()
+    base = mixed(rng, 3000)
+    items += [(base, RAW, CRC32), (base, ZLIB, NONE), (base[1000:], GZIP, NONE)]
+    packed, offs = pack_inputs(items[:-3])
+    offs += [len(packed), len(packed), len(packed) + 1000]
+    packed += base
+    order = list(range(len(items)))
+    rng.shuffle(order)
+    regions, off = [None] * len(items), 3
+    for i in order:
+        n = len(member(items[i][0], items[i][1], cfg)[0])
+        regions[i] = (off, n)
+        off += n + rng.randrange(0, 10)
+    res, out, _ = run(ctx, items, cfg, regions=regions, out_size=off + 7, out_shift=1, inputs=(packed, offs))
+    check(items, cfg, res, out, regions, "shuffled")
+
+
+@pytest.mark.parametrize("fmt", [RAW, ZLIB])
+def test_capacity(ctx, fmt):
+    """A stream that needs R bytes in a region of 0, 1, R - 1 and R (and, for a zlib member, regions that
+    end inside its trailer), between neighbours whose regions touch it: status, out_len == R, the stored
+    prefix, and the neighbours bit-exact."""
+    cfg = ("RLE_DYNAMIC", 65536, 32768)
+    rng = random.Random(9)
+    left, mid, right = salad(rng, 777), mixed(rng, 4000), mixed(rng, 1500)
+    R = len(member(mid, fmt, cfg)[0])
+    caps = [0, 1, R - 1, R] + ([R - 4, R - 3, R - 2] if fmt == ZLIB else [])
+    items, cl = [], []
+    for cap in caps:                        # all cases in one call: left | mid (cap) | right | left | mid ...
+        items += [(left, GZIP, NONE), (mid, fmt, CRC32), (right, RAW, ADLER32)]
+        cl += [len(member(left, GZIP, cfg)[0]), cap, len(member(right, RAW, cfg)[0])]
+    res = run_check(ctx, items, cfg, "capacity", caps=cl)
+    for k, cap in enumerate(caps):
+        assert res[3 * k + 1][0] == (0 if cap >= R else E_CAPACITY) and res[3 * k + 1][2] == R
+        assert res[3 * k][0] == 0 and res[3 * k + 2][0] == 0
+
+
+def test_checksums_and_trailers(ctx):
+    rng = random.Random(11)
+    bufs = [b"", b"\x00", b"\xff" * 70000, salad(rng, 5000), mixed(rng, 70001), rng.randbytes(1025), b"a" * 1024,
+            bytes(range(256)) * 5]
+    items = [(b, fmt, kind) for b in bufs for fmt, kind in
+             ((RAW, CRC32), (RAW, ADLER32), (RAW, NONE), (ZLIB, NONE), (GZIP, NONE), (ZLIB, CRC32), (GZIP, ADLER32))]
+    for cfg in (("RLE_DYNAMIC", 65536, 32768), ("LITERAL_STATIC", 259, 0)):
+        run_check(ctx, items, cfg, "checksums")
+
+
+@pytest.mark.parametrize("fmt", [ZLIB, GZIP])
+def test_members_round_trip(ctx, fmt):
+    """Context.deflate_members gives complete members: Python's zlib / gzip decode them, and so does
+    ctx.inflate_members, with the same checksum."""
+    import ndfl
+    rng = random.Random(13)
+    bufs = [b"", b"x", salad(rng, 3000), mixed(rng, 70000), b"\xff" * 70000, rng.randbytes(2000)]
+    members = ctx.deflate_members(bufs, fmt)
+    header = bytes((ndfl.ZlibMetadata.DEFAULT if fmt == ZLIB else ndfl.GzipMetadata()).header_bytes())
+    for b, m in zip(bufs, members):
+        assert m == header + oracle(b)[0] + trailer(b, fmt)
+        assert (zlib.decompress(m) if fmt == ZLIB else gzip.decompress(m)) == b
+    back = ctx.inflate_members(members, fmt, out_caps=[len(b) for b in bufs])
+    for b, m, (reason, out, bits, ck, hl) in zip(bufs, members, back):
+        assert reason is None and out == b and bits == 8 * len(m) and hl == len(header)
+        assert ck == checksum(b, fmt, NONE)
+    if fmt == GZIP:                         # other metadata: the header is the metadata's, the rest the same
+        meta = ndfl.GzipMetadata(fileName="a.txt", hasHeaderCrc=True, modificationTimeUnixS=1234567)
+        m = ctx.deflate_members([bufs[2]], GZIP, meta=meta, strategy="LITERAL_DYNAMIC", chunk_len=259)[0]
+        assert gzip.decompress(m) == bufs[2] and b"a.txt\0" in m[:20]
+        assert m.endswith(oracle(bufs[2], "LITERAL_DYNAMIC", 259, 32768)[0] + trailer(bufs[2], GZIP))
+
+
+def test_python_deflate_batch(ctx):
+    rng = random.Random(17)
+    bufs = [b"", salad(rng, 100), mixed(rng, 9000), b"q" * 300]
+    for sum_, ref in ((None, lambda b: 0), (CRC32, zlib.crc32), (ADLER32, zlib.adler32)):
+        got = ctx.deflate_batch(bufs, strategy="RLE_STATIC", chunk_len=1000, hist_limit=0, sum=sum_)
+        for b, (comp, bits, ck) in zip(bufs, got):
+            assert (comp, bits) == oracle(b, "RLE_STATIC", 1000, 0) and ck == ref(b)
+
+
+@functools.lru_cache(maxsize=None)
+def reuse_items():
+    """About 200 unlike streams in shuffled order: empty, text, long runs, random, multi-chunk."""
+    rng = random.Random(21)
+    items = []
+    for k in range(200):
+        kind = k % 6
+        if kind == 0:
+            buf = b""
+        elif kind == 1:
+            buf = salad(rng, rng.randrange(1, 3000))
+        elif kind == 2:
+            buf = bytes([rng.randrange(256)]) * rng.randrange(1, 5000)
+        elif kind == 3:
+            buf = rng.randbytes(rng.randrange(1, 1500))
+        elif kind == 4:
+            buf = mixed(rng, rng.randrange(1, 4000))
+        else:
+            buf = mixed(rng, 65536 + rng.randrange(0, 3000)) if k % 30 == 5 else bytes(rng.randrange(3) for _ in range(500))
+        items.append((buf, (RAW, ZLIB, GZIP)[rng.randrange(3)], (NONE, CRC32, ADLER32)[rng.randrange(3)]))
+    rng.shuffle(items)
+    return items
+
+
+def test_wave_reuse_one_wave(one_wave):
+    for cfg in (("RLE_DYNAMIC", 65536, 32768), ("RLE_DYNAMIC", 259, 32768)):
+        run_check(one_wave, reuse_items(), cfg, "one wave")
+
+
+def test_more_streams_than_waves(ctx):
+    rng = random.Random(23)
+    items = [(bytes(rng.randrange(4) for _ in range(rng.randrange(0, 41))), RAW, CRC32) for _ in range(5000)]
+    run_check(ctx, items, ("RLE_DYNAMIC", 65536, 32768), "5000 streams")
+
+
+def test_device_pointers_on_the_callers_stream(ctx):
+    """Input and output are torch tensors; the input is produced by a torch kernel on the current stream
+    immediately before the call, with no synchronize, and the output is read by torch right after."""
+    import torch
+    import ndfl
+    cfg = ("RLE_DYNAMIC", 65536, 32768)
+    items = reuse_items()[:60] + layout_items()
+    host_res, host_out, regions = run(ctx, items, cfg)
+    check(items, cfg, host_res, host_out, regions, "host")
+    packed, offs = pack_inputs(items)
+    recs = [(io, len(buf), o, c, fmt, kind) for (buf, fmt, kind), io, (o, c) in zip(items, offs, regions)]
+    n = len(packed)
+    # the device input is computed on the GPU: the packed bytes XOR 0x5A, XORed back by a torch kernel
+    masked = torch.frombuffer(bytearray(bytes(x ^ 0x5A for x in packed)), dtype=torch.uint8).cuda()
+    for shift in (0, 1):                                           # `in` and `out` at an odd address too
+        d_out = torch.full((len(host_out) + shift,), FILL, dtype=torch.uint8, device="cuda")
+        d_in = torch.empty(n + shift, dtype=torch.uint8, device="cuda")
+        d_in[shift:] = torch.bitwise_xor(masked, 0x5A)             # queued on the current stream, not waited for
+        res = ctx.deflate_batch_raw(d_in.data_ptr() + shift, n, d_out.data_ptr() + shift, len(host_out), recs, *cfg,
+                                    ndfl.IN_DEVICE | ndfl.OUT_DEVICE)
+        got = bytes(d_out.cpu().numpy())
+        assert res == host_res, shift
+        assert got[shift:] == host_out and got[:shift] == bytes([FILL]) * shift, shift
+    assert ctx.last_kernel_ms() > 0
+
+
+def test_arguments(ctx):
+    import ndfl
+    L = ndfl._lib.load()
+    s = b"abcdef" * 10
+    src = ctypes.create_string_buffer(s, len(s))
+    out = ctypes.create_string_buffer(bytes([FILL]) * 256, 256)
+    a_in, a_out = ctypes.addressof(src), ctypes.addressof(out)
+    ok = ("RLE_DYNAMIC", 65536, 32768)
+    assert ctx.deflate_batch_raw(a_in, len(s), a_out, 256, [], *ok, 0) == []
+    assert L.ndfl_deflate_batch(ctx._h, None, 0, None, 0, None, None, 0, 3, 65536, 32768, 0) == 0
+    one = [(0, len(s), 0, 100, RAW, NONE)]
+    res = (ndfl._lib.DeflateResult * 1)()
+    arr = (ndfl._lib.MemberItem * 1)(ndfl._lib.MemberItem(*one[0]))
+    before = bytes(res)
+    for args in ((None, len(s), a_out, 256, arr, res), (a_in, len(s), None, 256, arr, res),
+                 (a_in, len(s), a_out, 256, None, res), (a_in, len(s), a_out, 256, arr, None)):
+        assert L.ndfl_deflate_batch(ctx._h, *args, 1, 3, 65536, 32768, 0) == E_ARG
+    cases = [(E_ARG, items, ok) for items in (
+        [(0, len(s) + 1, 0, 100, RAW, NONE)], [(len(s) + 1, 0, 0, 100, RAW, NONE)], [(0, len(s), 200, 57, RAW, NONE)],
+        [(0, len(s), 257, 0, RAW, NONE)], [(0, len(s), 0, 100, RAW, NONE), (0, len(s), 99, 100, RAW, NONE)],
+        [(0, len(s), 50, 10, RAW, NONE), (0, len(s), 0, 100, RAW, NONE)], [(0, len(s), 1 << 63, 1 << 63, RAW, NONE)],
+        [(0, len(s), 0, 100, 3, NONE)], [(0, len(s), 0, 100, RAW, 3)])]
+    cases += [(E_ARG, one, ("RLE_DYNAMIC", 0, 32768)), (E_UNSUPPORTED, one, ("RLE_DYNAMIC", 65537, 32768)),
+              (E_ARG, one, ("RLE_DYNAMIC", 65536, 32769)), (E_UNSUPPORTED, one, ("FULL_DYNAMIC", 65536, 32768)),
+              (E_UNSUPPORTED, one, ("FULL_STATIC", 65536, 32768)), (E_UNSUPPORTED, one, ("UNCOMPRESSED", 65536, 32768)),
+              (E_ARG, one, (7, 65536, 32768))]
+    for code, items, cfg in cases:
+        with pytest.raises(ndfl.NdflError) as e:
+            ctx.deflate_batch_raw(a_in, len(s), a_out, 256, items, *cfg, 0)
+        assert e.value.code == code, (items, cfg)
+        assert out.raw == bytes([FILL]) * 256, (items, cfg)
+    # the raw call leaves `results` untouched on an error
+    assert L.ndfl_deflate_batch(ctx._h, a_in, len(s), a_out, 256, arr, res, 1, 5, 65536, 32768, 0) == E_UNSUPPORTED
+    assert L.ndfl_deflate_batch(ctx._h, a_in, len(s), a_out, 256, arr, res, 1, 3, 0, 32768, 0) == E_ARG
+    assert bytes(res) == before and out.raw == bytes([FILL]) * 256
+    # regions that only touch, and an empty region inside another, are fine
+    items = [(0, len(s), 0, 60, RAW, NONE), (0, len(s), 60, 60, RAW, NONE), (0, 0, 30, 0, RAW, NONE)]
+    got = ctx.deflate_batch_raw(a_in, len(s), a_out, 256, items, *ok, 0)
+    comp, bits = oracle(s)
+    empty, ebits = oracle(b"")
+    assert got == [(0, 0, len(comp), bits), (0, 0, len(comp), bits), (E_CAPACITY, 0, len(empty), ebits)]
+    assert out.raw[:len(comp)] == comp and out.raw[60:60 + len(comp)] == comp
+    assert out.raw[len(comp):60] == bytes([FILL]) * (60 - len(comp)) and out.raw[60 + len(comp):] == bytes([FILL]) * (196 - len(comp))
+
+
+@pytest.mark.parametrize("strategy", STRATEGIES)
+def test_equals_the_one_stream_encoder(ctx, strategy):
+    """GPU against GPU: the batch's bytes for a 200,000-byte buffer are ctx.deflate's."""
+    buf = mixed(random.Random(31), 200000)
+    for chunk_len, hist_limit in ((65536, 32768), (10000, 0)):
+        comp, bits, _ = ctx.deflate_batch([buf], strategy, chunk_len, hist_limit)[0]
+        assert comp == ctx.deflate(buf, strategy, chunk_len, hist_limit)
+        assert (bits + 7) // 8 == len(comp)
