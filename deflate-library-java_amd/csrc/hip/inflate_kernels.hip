@@ -1151,6 +1151,7 @@ struct InflateScratch {
     double last_ms_find = 0, last_ms_count = 0, last_ms_emit = 0, last_ms_wall = 0;
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     uint64_t repairs = 0, chains = 0, candidates = 0, resolved_groups = 0, flat_chains = 0;
+    uint64_t pending_after_dev = 0;                   // 32-byte groups still pending after the device-queued resolve rounds
     void* h_cnt = nullptr;                            // pinned: resolve list size
     void* d_info = nullptr;                           // device-side linking: summary (LI_*)
     void* h_info = nullptr;                           //   and its pinned host copy
@@ -1698,6 +1699,7 @@ static int inflate_devlink(InflateScratch& S, hipStream_t s, const uint32_t* d_w
     S.repairs = 0;
     if (lflags & LF_CAPACITY) { *out_len = hinfo[LI_TOTAL]; return -3; }
     const uint32_t pending_left = (uint32_t)(hinfo[LI_WORDS - 1] & 0xFFFFFFFFu);
+    S.pending_after_dev = deferred ? 0 : pending_left;
     if (!deferred && pending_left) {
         uint64_t groups = 0;
         rc = resolve_rounds(S, s, d_out, nbytes, &groups);     // (the rest, with the host's checks)
@@ -1865,6 +1867,7 @@ static int inflate_run(InflateScratch& S, hipStream_t s, const uint8_t* in, uint
     *out_len = 0;
     *consumed_bits = 0;
     S.pending = false;
+    if (!probe_sync) S.pending_after_dev = 0;
     const bool htime = S.knobs.host_times;
     auto hnow = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double ht[8] = {hnow(), 0, 0, 0, 0, 0, 0, 0};

@@ -258,11 +258,12 @@ class Context:
         return load().ndfl_ctx_last_kernel_ms(self._h)
 
     def timings(self):
-        """{'deflate', 'inflate_find', 'inflate_count', 'inflate_emit', 'inflate_span'} in ms."""
-        arr = (ctypes.c_double * 9)()
-        load().ndfl_ctx_timings(self._h, arr, 9)
+        """{'deflate', 'inflate_find', 'inflate_count', 'inflate_emit', 'inflate_span'} in ms, then the
+        last decode's counts (include/ndfl.h, ndfl_ctx_timings)."""
+        arr = (ctypes.c_double * 10)()
+        load().ndfl_ctx_timings(self._h, arr, 10)
         keys = ["deflate", "inflate_find", "inflate_count", "inflate_emit", "inflate_span", "inflate_chains",
-                "inflate_repairs", "inflate_candidates", "inflate_flat_chains"]
+                "inflate_repairs", "inflate_candidates", "inflate_flat_chains", "inflate_pending_after_dev_rounds"]
         return dict(zip(keys, list(arr)))
 
     # -- raw C-ABI wrappers ------------------------------------------------------------------

@@ -95,7 +95,10 @@ double ndfl_ctx_last_kernel_ms(ndfl_ctx* ctx);
 /* Device-time breakdown of the last calls (ms): [0] deflate kernel, [1] inflate finder,
  * [2] inflate count, [3] inflate emit, [4] inflate device span, [5] linked chains, [6] repaired
  * boundaries, [7] header candidates, [8] chains whose first block the count pass decoded one lane
- * per block (escape-prefix literal codes).  Returns the number of entries written (<= 9). */
+ * per block (escape-prefix literal codes), [9] 32-byte output groups still pending after the six
+ * device-queued resolve rounds of the last ndfl_inflate / ndfl_inflate_range (> 0: the host-checked
+ * rounds ran; 0 on the host-link path and for NDFL_DICT_DEFERRED decodes).  Returns the number of
+ * entries written (<= 10). */
 int ndfl_ctx_timings(ndfl_ctx* ctx, double* ms, int n);
 /* The reserved symbol behind the last ndfl_inflate / ndfl_inflate_range that returned
  * NDFL_RESERVED_LENGTH_SYMBOL (286 or 287) or NDFL_RESERVED_DISTANCE_SYMBOL (30 or 31), else -1:
