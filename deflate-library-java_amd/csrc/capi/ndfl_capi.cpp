@@ -8,6 +8,7 @@
 #include "../hip/inflate_kernels.hip"
 #include "../hip/inflate_batch.hip"
 #include "../hip/deflate_batch.hip"
+#include "../hip/deflate_batch_lz.hip"
 
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -77,6 +78,7 @@ struct ndfl_ctx {
     uint32_t parent_len = 0;        // internal: history rule of BinarySplit sub-blocks (0: chunk_len)
     InflateScratch inf;
     BatchScratch batch;             // ndfl_inflate_batch: items / results / host-output staging
+    BatchLzScratch batch_lz;        // ndfl_deflate_batch_lz77: the waves' link rings and token lists
     uint32_t* h_pinned = nullptr;   // small pinned area for results
     Knobs knobs;                    // switches read once at ndfl_ctx_create (ndfl_common.hpp)
     int err_sym = -1;               // the last decode's reserved symbol (ndfl_ctx_error_symbol), or -1
@@ -175,6 +177,7 @@ int ndfl_ctx_destroy(ndfl_ctx* c) {
     for (int k = 0; k < 16; k++) { c->d_mstreams[k].release(); c->d_mbits[k].release(); }
     c->inf.release();
     c->batch.release();
+    c->batch_lz.release();
     if (c->h_pinned) hipHostFree(c->h_pinned);
     if (c->ev0) hipEventDestroy(c->ev0);
     if (c->ev1) hipEventDestroy(c->ev1);
@@ -1096,9 +1099,43 @@ int ndfl_deflate_batch(ndfl_ctx* c, const uint8_t* in, uint64_t in_size, uint8_t
     for (uint32_t i = 0; i < n; i++)
         if (items[i].format > NDFL_FMT_GZIP || items[i].sum > NDFL_SUM_ADLER32) return NDFL_E_ARG;
     HIPCHK(hipSetDevice(c->device));
-    const int r = deflate_batch_run(c->batch, &c->d_in.p, &c->d_in.cap, c->knobs, ordered_stream(c), c->ev0, c->ev1, in,
-                                    out, items, results, n, rle, dyn, chunk_len, hist_limit, flags,
-                                    c->d_tabs.as<uint32_t>(), &c->last_ms);
+    const int r = deflate_batch_run(c->batch, &c->d_in.p, &c->d_in.cap, ordered_stream(c), c->ev0, c->ev1, in, out, items,
+                                    results, n, flags,
+                                    BatchRleLaunch{c->knobs, n, rle, dyn, chunk_len, hist_limit, c->d_tabs.as<uint32_t>()},
+                                    &c->last_ms);
+    if (r) return r == -4 ? NDFL_E_DEVICE : NDFL_E_INTERNAL;
+    return NDFL_OK;
+}
+
+int ndfl_deflate_batch_lz77(ndfl_ctx* c, const uint8_t* in, uint64_t in_size, uint8_t* out, uint64_t out_size,
+                            const ndfl_member_item* items, ndfl_deflate_result* results, uint32_t n, int dynamic,
+                            int min_run, int max_run, int min_dist, int max_dist, uint32_t chunk_len,
+                            uint32_t hist_limit, uint32_t flags) {
+    if (!c) return NDFL_E_ARG;
+    if (n == 0) return NDFL_OK;
+    const bool literal_only = min_run == 0 && max_run == 0 && min_dist == 0 && max_dist == 0;   // (:29-31)
+    if (!literal_only && !(3 <= min_run && min_run <= max_run && max_run <= 258 && 1 <= min_dist &&
+                           min_dist <= max_dist && max_dist <= 32768))
+        return NDFL_E_ARG;                                                                     // (:32-38)
+    // the literal-only and the distance-1 forms are ndfl_deflate_batch's presets, as in ndfl_deflate_chunks_lz77
+    if (literal_only || (min_run == 3 && max_run == 258 && min_dist == 1 && max_dist == 1))
+        return ndfl_deflate_batch(c, in, in_size, out, out_size, items, results, n,
+                                  literal_only ? (dynamic ? NDFL_LITERAL_DYNAMIC : NDFL_LITERAL_STATIC)
+                                               : (dynamic ? NDFL_RLE_DYNAMIC : NDFL_RLE_STATIC),
+                                  chunk_len, hist_limit, flags);
+    if (chunk_len == 0 || hist_limit > 32768) return NDFL_E_ARG;
+    if (chunk_len > (uint32_t)MAX_CHUNK) return NDFL_E_UNSUPPORTED;
+    if (!batch_regions_valid(in, in_size, out, out_size, items, results, n)) return NDFL_E_ARG;
+    for (uint32_t i = 0; i < n; i++)
+        if (items[i].format > NDFL_FMT_GZIP || items[i].sum > NDFL_SUM_ADLER32) return NDFL_E_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    BatchLzLaunch launch{c->batch_lz, c->knobs, items, n, dblz::Args{}};
+    launch.a.chunk_len = chunk_len; launch.a.hist_limit = hist_limit; launch.a.dynamic = dynamic != 0;
+    launch.a.min_run = (uint32_t)min_run; launch.a.max_run = (uint32_t)max_run;
+    launch.a.min_dist = (uint32_t)min_dist; launch.a.max_dist = (uint32_t)max_dist;
+    launch.a.crc_tab = c->d_tabs.as<uint32_t>();
+    const int r = deflate_batch_run(c->batch, &c->d_in.p, &c->d_in.cap, ordered_stream(c), c->ev0, c->ev1, in, out, items,
+                                    results, n, flags, launch, &c->last_ms);
     if (r) return r == -4 ? NDFL_E_DEVICE : NDFL_E_INTERNAL;
     return NDFL_OK;
 }

@@ -242,6 +242,80 @@ __device__ __forceinline__ uint32_t wave_xor_l(uint32_t x, int lane) {
     return x;
 }
 
+// A lane's vcnt (<= BPL) bytes from p as four words (zero past them), from the aligned words that hold them.
+__device__ __forceinline__ void load_lane(const uint8_t* p, uint32_t vcnt, uint32_t& w0, uint32_t& w1, uint32_t& w2,
+                                          uint32_t& w3) {
+    w0 = 0; w1 = 0; w2 = 0; w3 = 0;
+    if (vcnt == BPL) {
+        const uint32_t mis = (uint32_t)((uintptr_t)p & 3);
+        const uint32_t* q = (const uint32_t*)(p - mis);
+        const uint32_t a0 = q[0], a1 = q[1], a2 = q[2], a3 = q[3];
+        const uint32_t a4 = mis ? q[4] : 0u;                 // (holds the lane's last byte: readable)
+        const uint32_t sh = 8 * mis;
+        w0 = __builtin_amdgcn_alignbit(a1, a0, sh);
+        w1 = __builtin_amdgcn_alignbit(a2, a1, sh);
+        w2 = __builtin_amdgcn_alignbit(a3, a2, sh);
+        w3 = __builtin_amdgcn_alignbit(a4, a3, sh);
+    } else if (vcnt) {
+#pragma unroll
+        for (uint32_t i = 0; i < BPL; i++) {
+            if (i < vcnt) {
+                const uint32_t b = (uint32_t)p[i] << (8 * (i & 3));
+                if (i < 4) w0 |= b; else if (i < 8) w1 |= b; else if (i < 12) w2 |= b; else w3 |= b;
+            }
+        }
+    }
+}
+
+// A step's L bytes (lane `lane` holds the vcnt bytes from step position t0 on, load_lane) into the
+// checksum ck (kind: NDFL_SUM_*).
+__device__ __forceinline__ void fold_step(uint64_t v_tab, uint32_t kind, int lane, uint32_t L, uint32_t t0, uint32_t vcnt,
+                                          uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t& ck) {
+    const uint32_t after = vcnt ? L - (t0 + vcnt) : 0u;      // the step's bytes behind this lane's
+    if (kind == NDFL_SUM_CRC32) {
+        const uint32_t* T0 = (const uint32_t*)(uintptr_t)to_s(v_tab);     // slicing-by-4 tables, then x^(8k)
+        const uint32_t* T1 = T0 + 256;
+        const uint32_t* T2 = T0 + 512;
+        const uint32_t* T3 = T0 + 768;
+        const uint32_t* crc_x = T0 + 1024;
+        uint32_t cr = 0;
+        const uint32_t nfull = vcnt >> 2;
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++) {
+            if (k < nfull) {
+                const uint32_t x = cr ^ (k == 0 ? w0 : k == 1 ? w1 : k == 2 ? w2 : w3);
+                cr = T3[x & 0xFF] ^ T2[(x >> 8) & 0xFF] ^ T1[(x >> 16) & 0xFF] ^ T0[x >> 24];
+            }
+        }
+        for (uint32_t i = nfull * 4; i < vcnt; i++) cr = T0[(cr ^ byte_at(w0, w1, w2, w3, i)) & 0xFF] ^ (cr >> 8);
+        uint32_t contrib = 0;
+        if (vcnt) {
+            uint32_t sh = crc_x[64 + (after >> 6)];
+            if (after & 63) sh = crc_multmodp(crc_x[after & 63], sh);
+            contrib = crc_multmodp(sh, cr);
+        }
+        const uint32_t span = wave_xor_l(contrib, lane);
+        uint32_t xl = crc_x[64 + (L >> 6)];
+        if (L & 63) xl = crc_multmodp(crc_x[L & 63], xl);
+        ck = crc_multmodp(xl, ck) ^ span;
+    } else if (kind == NDFL_SUM_ADLER32) {
+        // per lane s1 = sum of its bytes, s2 = sum of its running s1; the bytes behind the lane
+        // count its s1 once each.  s1 <= 4,080, s2 <= 34,680, s1 * after < 2^22: 64 of them < 2^32
+        uint32_t s1 = 0, s2 = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < BPL; i++) {
+            if (i < vcnt) {
+                s1 += ((i < 4 ? w0 : i < 8 ? w1 : i < 12 ? w2 : w3) >> (8 * (i & 3))) & 0xFFu;
+                s2 += s1;
+            }
+        }
+        const uint32_t S1 = wave_sum_l(s1, lane), T = wave_sum_l(s2 + s1 * after, lane);
+        const uint32_t A = ck & 0xFFFFu, B = ck >> 16;
+        const uint32_t nb = (B + (L * A) % 65521u + T % 65521u) % 65521u, na = (A + S1) % 65521u;
+        ck = nb << 16 | na;
+    }
+}
+
 // The carried piece's tokens, by lane 0 (hist) or counted by all and put by lane 0 (emit).
 template <bool EMIT>
 __device__ __forceinline__ void close_carry(Lds& S, BitOut& bo, const Codes& cd, uint32_t cval, uint32_t clen,
@@ -282,72 +356,10 @@ __device__ __forceinline__ uint32_t walk_chunk(bool rle, uint64_t v_tab, Lds& S,
         const uint32_t t0 = (uint32_t)lane * BPL;
         const uint32_t L = min(STEP, len_c - sb);
         const uint32_t vcnt = L > t0 ? min(BPL, L - t0) : 0u;
-        // ---- load: 16 bytes per lane, from the aligned words that hold them ---------------------
-        uint32_t w0 = 0, w1 = 0, w2 = 0, w3 = 0;
-        const uint8_t* p = cp + sb + t0;
-        if (vcnt == BPL) {
-            const uint32_t mis = (uint32_t)((uintptr_t)p & 3);
-            const uint32_t* q = (const uint32_t*)(p - mis);
-            const uint32_t a0 = q[0], a1 = q[1], a2 = q[2], a3 = q[3];
-            const uint32_t a4 = mis ? q[4] : 0u;                 // (holds the lane's last byte: readable)
-            const uint32_t sh = 8 * mis;
-            w0 = __builtin_amdgcn_alignbit(a1, a0, sh);
-            w1 = __builtin_amdgcn_alignbit(a2, a1, sh);
-            w2 = __builtin_amdgcn_alignbit(a3, a2, sh);
-            w3 = __builtin_amdgcn_alignbit(a4, a3, sh);
-        } else if (vcnt) {
-#pragma unroll
-            for (uint32_t i = 0; i < BPL; i++) {
-                if (i < vcnt) {
-                    const uint32_t b = (uint32_t)p[i] << (8 * (i & 3));
-                    if (i < 4) w0 |= b; else if (i < 8) w1 |= b; else if (i < 12) w2 |= b; else w3 |= b;
-                }
-            }
-        }
-        const uint32_t after = vcnt ? L - (t0 + vcnt) : 0u;      // the step's bytes behind this lane's
+        uint32_t w0, w1, w2, w3;
+        load_lane(cp + sb + t0, vcnt, w0, w1, w2, w3);
         // ---- checksum of the bytes on their way through -------------------------------------------
-        if (EMIT && kind == NDFL_SUM_CRC32) {
-            const uint32_t* T0 = (const uint32_t*)(uintptr_t)to_s(v_tab);     // slicing-by-4 tables, then x^(8k)
-            const uint32_t* T1 = T0 + 256;
-            const uint32_t* T2 = T0 + 512;
-            const uint32_t* T3 = T0 + 768;
-            const uint32_t* crc_x = T0 + 1024;
-            uint32_t cr = 0;
-            const uint32_t nfull = vcnt >> 2;
-#pragma unroll
-            for (uint32_t k = 0; k < 4; k++) {
-                if (k < nfull) {
-                    const uint32_t x = cr ^ (k == 0 ? w0 : k == 1 ? w1 : k == 2 ? w2 : w3);
-                    cr = T3[x & 0xFF] ^ T2[(x >> 8) & 0xFF] ^ T1[(x >> 16) & 0xFF] ^ T0[x >> 24];
-                }
-            }
-            for (uint32_t i = nfull * 4; i < vcnt; i++) cr = T0[(cr ^ byte_at(w0, w1, w2, w3, i)) & 0xFF] ^ (cr >> 8);
-            uint32_t contrib = 0;
-            if (vcnt) {
-                uint32_t sh = crc_x[64 + (after >> 6)];
-                if (after & 63) sh = crc_multmodp(crc_x[after & 63], sh);
-                contrib = crc_multmodp(sh, cr);
-            }
-            const uint32_t span = wave_xor_l(contrib, lane);
-            uint32_t xl = crc_x[64 + (L >> 6)];
-            if (L & 63) xl = crc_multmodp(crc_x[L & 63], xl);
-            ck = crc_multmodp(xl, ck) ^ span;
-        } else if (EMIT && kind == NDFL_SUM_ADLER32) {
-            // per lane s1 = sum of its bytes, s2 = sum of its running s1; the bytes behind the lane
-            // count its s1 once each.  s1 <= 4,080, s2 <= 34,680, s1 * after < 2^22: 64 of them < 2^32
-            uint32_t s1 = 0, s2 = 0;
-#pragma unroll
-            for (uint32_t i = 0; i < BPL; i++) {
-                if (i < vcnt) {
-                    s1 += ((i < 4 ? w0 : i < 8 ? w1 : i < 12 ? w2 : w3) >> (8 * (i & 3))) & 0xFFu;
-                    s2 += s1;
-                }
-            }
-            const uint32_t S1 = wave_sum_l(s1, lane), T = wave_sum_l(s2 + s1 * after, lane);
-            const uint32_t A = ck & 0xFFFFu, B = ck >> 16;
-            const uint32_t nb = (B + (L * A) % 65521u + T % 65521u) % 65521u, na = (A + S1) % 65521u;
-            ck = nb << 16 | na;
-        }
+        if (EMIT) fold_step(v_tab, kind, lane, L, t0, vcnt, w0, w1, w2, w3, ck);
         // ---- piece starts: bit i = byte i differs from the byte before it ---------------------------
         uint32_t F;
         {
@@ -554,14 +566,40 @@ ndfl_deflate_batch_kernel(dbat::Args a) {
 }
 
 // ---- host side ------------------------------------------------------------------------------------
-// The batch on stream s (arguments already validated): one launch, one host sync.  Host input is
-// staged in B.d_in (the span of `in` the items cover), host output in B.d_out as inflate_batch_run
-// does, and only each stream's stored bytes are copied into `out`.
-static int deflate_batch_run(BatchScratch& B, void** d_in, size_t* d_in_cap, const Knobs& knobs, hipStream_t s,
-                             hipEvent_t e0, hipEvent_t e1, const uint8_t* in, uint8_t* out,
-                             const ndfl_member_item* items, ndfl_deflate_result* results, uint32_t n, int rle, int dyn,
-                             uint32_t chunk_len, uint32_t hist_limit, uint32_t flags, const uint32_t* crc_tabs,
-                             double* last_ms) {
+// The launch of ndfl_deflate_batch_kernel for deflate_batch_run: the grid, then the kernel between the
+// two events.
+struct BatchRleLaunch {
+    const Knobs& knobs;
+    uint32_t n;
+    int rle, dyn;
+    uint32_t chunk_len, hist_limit;
+    const uint32_t* crc_tabs;
+    int operator()(hipStream_t s, const uint8_t* d_src, uint8_t* d_out, const ndfl_member_item* d_items,
+                   ndfl_deflate_result* d_res, uint32_t* d_ticket, hipEvent_t e0, hipEvent_t e1) {
+        static const uint32_t auto_grid = wave_grid(ndfl_deflate_batch_kernel, 256 * 16);
+        uint32_t grid = std::min(n, auto_grid);
+        if (knobs.batch_waves) grid = std::min(grid, knobs.batch_waves);
+        if (knobs.stats) fprintf(stderr, "[ndfl] deflate batch: %u streams, %u waves (of %u)\n", n, grid, auto_grid);
+        dbat::Args a;
+        a.in = d_src; a.out = d_out; a.items = d_items; a.results = d_res; a.n = n;
+        a.chunk_len = chunk_len; a.ticket = d_ticket; a.hist_enabled = hist_limit > 0; a.rle = rle; a.dynamic = dyn;
+        a.crc_tab = crc_tabs; a.crc_x = crc_tabs + 1024;
+        INF_CHK(hipEventRecord(e0, s));
+        hipLaunchKernelGGL(ndfl_deflate_batch_kernel, dim3(grid), dim3(64), 0, s, a);
+        INF_CHK(hipGetLastError());
+        INF_CHK(hipEventRecord(e1, s));
+        return 0;
+    }
+};
+
+// The batch on stream s (arguments already validated): one launch (`launch`: BatchRleLaunch, or
+// deflate_batch_lz.hip's BatchLzLaunch), one host sync.  Host input is staged in B.d_in (the span of
+// `in` the items cover), host output in B.d_out as inflate_batch_run does, and only each stream's
+// stored bytes are copied into `out`.
+template <class Launch>
+static int deflate_batch_run(BatchScratch& B, void** d_in, size_t* d_in_cap, hipStream_t s, hipEvent_t e0, hipEvent_t e1,
+                             const uint8_t* in, uint8_t* out, const ndfl_member_item* items,
+                             ndfl_deflate_result* results, uint32_t n, uint32_t flags, Launch launch, double* last_ms) {
     uint64_t ilo = ~0ull, ihi = 0, lo = ~0ull, hi = 0;
     for (uint32_t i = 0; i < n; i++) {
         if (items[i].in_len) {
@@ -594,18 +632,10 @@ static int deflate_batch_run(BatchScratch& B, void** d_in, size_t* d_in_cap, con
         if (hi > lo) INF_CHK(inf_ensure(&B.d_out, &B.d_out_cap, hi - lo));
         d_out = (uint8_t*)B.d_out - (hi > lo ? lo : 0);
     }
-    static const uint32_t auto_grid = wave_grid(ndfl_deflate_batch_kernel, 256 * 16);
-    uint32_t grid = std::min(n, auto_grid);
-    if (knobs.batch_waves) grid = std::min(grid, knobs.batch_waves);
-    if (knobs.stats) fprintf(stderr, "[ndfl] deflate batch: %u streams, %u waves (of %u)\n", n, grid, auto_grid);
-    dbat::Args a;
-    a.in = d_src; a.out = d_out; a.items = (const ndfl_member_item*)B.d_items; a.results = d_res; a.n = n;
-    a.chunk_len = chunk_len; a.ticket = d_ticket; a.hist_enabled = hist_limit > 0; a.rle = rle; a.dynamic = dyn;
-    a.crc_tab = crc_tabs; a.crc_x = crc_tabs + 1024;
-    INF_CHK(hipEventRecord(e0, s));
-    hipLaunchKernelGGL(ndfl_deflate_batch_kernel, dim3(grid), dim3(64), 0, s, a);
-    INF_CHK(hipGetLastError());
-    INF_CHK(hipEventRecord(e1, s));
+    {
+        const int r = launch(s, d_src, d_out, (const ndfl_member_item*)B.d_items, d_res, d_ticket, e0, e1);
+        if (r) return r;
+    }
     INF_CHK(hipMemcpyAsync(results, d_res, res_b, hipMemcpyDeviceToHost, s));
     if (!out_dev && hi > lo) {
         h_span.resize(hi - lo);

@@ -1,0 +1,467 @@
+// deflate_batch_lz.hip -- batched LZ77 deflate: many independent buffers compressed in one launch with
+// any Lz77Huffman(dynamic, minRun, maxRun, minDist, maxDist), FULL_* among them
+// (ndfl_deflate_batch_lz77, include/ndfl.h).  The LZ77 counterpart of deflate_batch.hip, whose launch
+// shape, bit buffer, region stores, checksum folding and trailers it shares (dbat::): a persistent grid
+// of one-wave workgroups, an atomic ticket over the stream indices, each stream encoded chunk by chunk,
+// serially, by one wave that waits on no other.
+//
+// ndfl_deflate_chunks_lz77 searches with three kernels over one staging buffer with one history start
+// (LzArgs.vstart).  Here a wave carries its stream's history itself: the hash chains of the stream run
+// on across its chunk ends, and a chunk's window starts at its own stream offset
+// cs - min(hist_limit, cs), never at a neighbour's bytes.  Per chunk (= block), in steps of 64
+// consecutive positions, one lane per position:
+//   link    the position's 3-byte prefix is hashed (HBITS bits) and linked to the previous position of
+//           the stream in the same bucket through a head table in LDS; positions of one step that share
+//           a bucket are resolved in position order by readlane, as ndfl_lz_links_kernel does.  link[q]
+//           is a u16 distance (0: none within 32 KiB) in the wave's ring in device memory.
+//   search  each lane walks its position's chain nearest-first and keeps strictly longer runs: the loop
+//           of ndfl_lz_match_kernel, i.e. the longest run in the window, the smallest distance among
+//           equal runs (D/comp/Lz77Huffman.java:68-90).  Bytes are read from `in`.
+//   parse   the greedy parse chases through the 64 results with readlane; a run that ends past the step
+//           carries the next parse position into the next step (a run is capped at the chunk's end).
+//           Each token (run << 16 | dist - 1, or the literal) goes to the wave's token list in device
+//           memory and, for dynamic codes, into the LDS histograms.
+// then build_block_codes<64, true>, the header, and the tokens again, 64 a step: each lane's bits
+// counted, wave-scanned and put into the LDS bit buffer (a token is <= 48 bits).
+// The input's checksum is folded in a walk of its own over the chunk (16 bytes per lane, as
+// dbat::walk_chunk folds it).
+//
+// Device memory of a wave (owned by the context, BatchLzScratch): the link ring and the token list.
+// The same wave writes and reads them, other lanes' values after a __syncthreads() (a workgroup-scope
+// fence: one CU, one vector L1).
+//
+// No scratch memory: everything is forced inline, no per-lane array is indexed by a variable, and the
+// lane index is an opaque_lane() (see deflate_batch.hip).
+// D/ = src/io/nayuki/deflate/ in the reference
+#pragma once
+#include "deflate_batch.hip"
+
+namespace dblz {
+
+using dbat::BitOut;
+using dbat::make_room;
+using dbat::OBW;
+using dbat::rfl;
+using dbat::store_bytes;
+using dbat::to_s;
+using dbat::to_v;
+
+constexpr uint32_t HBITS = 12;                // head table: 4,096 x u16
+constexpr uint32_t NHEAD = 1u << HBITS;
+constexpr uint32_t HNONE = 0xFFFFu;           // empty head entry
+// A head entry is a position's offset from a base that follows the stream: when a step starts REBASE_AT
+// or more past the base, the base moves up by REBASE and the entries below it are emptied.  Offsets stay
+// below REBASE_AT + 2 * 64 < HNONE, and an emptied entry was more than 32,768 before the step.
+constexpr uint32_t REBASE_AT = 49152, REBASE = 16384;
+constexpr uint32_t MAXD = 32768;              // the largest distance
+constexpr uint32_t RING_MAX = 65536;          // link ring entries (a power of two >= MAXD + 64)
+static_assert(REBASE_AT + 128 < HNONE && REBASE_AT - REBASE >= MAXD && RING_MAX >= MAXD + 64, "head offsets and ring");
+static_assert(31 + 64 * 48 <= 32 * OBW, "a step of 64 tokens fits the flushed bit buffer");
+
+__device__ __forceinline__ uint32_t hash3(uint32_t k) { return (k * 2654435761u) >> (32 - HBITS); }
+
+struct Args {
+    const uint8_t* in;
+    uint8_t* out;
+    const ndfl_member_item* items;
+    ndfl_deflate_result* results;
+    uint32_t n;
+    uint32_t chunk_len;
+    uint32_t* ticket;         // zeroed
+    uint32_t hist_limit;
+    int32_t dynamic;
+    uint32_t min_run, max_run, min_dist, max_dist;    // 3 <= min_run <= max_run <= 258, 1 <= min_dist <= max_dist <= 32768
+    const uint32_t* crc_tab;  // slicing-by-4 tables (1024 u32), then x^(8k) k<64, then x^(8*64k) k<1024
+    uint16_t* ring;           // ring_mask + 1 links per wave
+    uint32_t ring_mask;       // entries - 1: RING_MAX - 1, or a power of two >= the longest in_len, - 1
+    uint32_t* toks;           // tok_cap tokens per wave
+    uint32_t tok_cap;         // >= min(chunk_len, longest in_len)
+};
+
+// LDS of one wave: 20,824 bytes, 7 waves per CU (160 KiB / 20,824 = 7.87).
+struct Lds {
+    HuffScr scr;              // (first: pm_lengths reads its keys 16 bytes at a time)
+    uint32_t litCode[288];    // rev(code) | len << 16
+    uint32_t distCode[32];
+    uint32_t obuf[OBW + 1];   // bit buffer (dbat::BitOut)
+    uint16_t head[NHEAD];     // bucket -> offset of its last position from the base, or HNONE
+    uint32_t ticket;
+};
+
+struct Search {
+    uint32_t min_run, max_run, min_dist, max_dist;
+};
+
+// Bytes [r, r + 4) of P, zero from P + rend on (nothing at or past P + rend is read).
+__device__ __forceinline__ uint32_t ld4(const uint8_t* P, uint32_t r, uint32_t rend) {
+    uint32_t w = 0;
+    if (r + 4 <= rend) {
+        __builtin_memcpy(&w, P + r, 4);
+    } else {
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++)
+            if (r + k < rend) w |= (uint32_t)P[r + k] << (8 * k);
+    }
+    return w;
+}
+
+// The chunk's bytes into the checksum ck (kind: NDFL_SUM_*), 64 lanes x 16 bytes a step: the load and the
+// folding of dbat::walk_chunk<true>.
+__device__ __forceinline__ void fold_chunk(uint64_t v_tab, const uint8_t* cp, uint32_t len_c, uint32_t kind, uint32_t& ck) {
+    using dbat::BPL;
+    using dbat::STEP;
+    if (kind == NDFL_SUM_NONE) return;
+    for (uint32_t sb = 0; sb < len_c; sb += STEP) {
+        const int lane = opaque_lane();
+        const uint32_t t0 = (uint32_t)lane * BPL;
+        const uint32_t L = min(STEP, len_c - sb);
+        const uint32_t vcnt = L > t0 ? min(BPL, L - t0) : 0u;
+        uint32_t w0, w1, w2, w3;
+        dbat::load_lane(cp + sb + t0, vcnt, w0, w1, w2, w3);
+        dbat::fold_step(v_tab, kind, lane, L, t0, vcnt, w0, w1, w2, w3, ck);
+    }
+}
+
+// Link, search and parse of one chunk.  Positions are window-relative: P = the stream's byte at offset
+// hs = cs - min(hist_limit, cs), the chunk starts at rc0 = cs - hs, P + rend ends what may be read (the
+// stream's end, or a few bytes past the chunk's).  hsm = (uint32_t)hs: the ring slot of position r is
+// (hsm + r) & mask.  cb = cs - the head table's base, carried from chunk to chunk.  Returns the number
+// of tokens stored in toks[].
+__device__ __forceinline__ uint32_t lz_chunk(Lds& S, const Search& sp, const uint8_t* P, uint32_t rc0, uint32_t len_c,
+                                             uint32_t rend, uint32_t hsm, uint16_t* ring, uint32_t mask, uint32_t* toks,
+                                             bool dyn, uint32_t& cb) {
+    uint32_t pos = 0;                         // the next parse position (chunk-relative, <= len_c)
+    uint32_t ntok = 0;
+    for (uint32_t sb = 0; sb < len_c; sb += 64) {
+        const int lane = opaque_lane();
+        const uint32_t t = sb + (uint32_t)lane;
+        const bool inb = t < len_c;
+        const uint32_t ri = rc0 + t;
+        if (cb + sb >= REBASE_AT) {           // (a step adds 64: one move keeps cb + sb below REBASE_AT)
+            for (uint32_t k = (uint32_t)lane; k < NHEAD; k += 64) {
+                const uint32_t v = S.head[k];
+                S.head[k] = (uint16_t)((v != HNONE && v >= REBASE) ? v - REBASE : HNONE);
+            }
+            cb -= REBASE;
+            __syncthreads();
+        }
+        // ---- link: the stream's last two positions have no 3-byte prefix and are not linked -------
+        const uint32_t wi0 = inb ? ld4(P, ri, rend) : 0u;
+        const bool hasp = inb && ri + 2 < rend;
+        uint32_t h = 0x10000u + (uint32_t)lane;                   // a bucket of its own
+        if (hasp) h = hash3(wi0 & 0xFFFFFFu);
+        int prevLane = -1;
+        bool last = true;
+#pragma unroll 8
+        for (int k = 0; k < 64; k++) {
+            const uint32_t hk = (uint32_t)__builtin_amdgcn_readlane((int)h, k);
+            const bool eq = hk == h;
+            if (eq && k < lane) prevLane = k;
+            if (eq && k > lane) last = false;
+        }
+        const uint32_t off = cb + t;
+        uint32_t d = 0;
+        if (hasp) {
+            if (prevLane >= 0) {
+                d = (uint32_t)(lane - prevLane);
+            } else {
+                const uint32_t hv = S.head[h];
+                if (hv != HNONE) { d = off - hv; if (d > MAXD) d = 0; }
+            }
+        }
+        if (hasp && last) S.head[h] = (uint16_t)off;              // (one wave: after every lane's read above)
+        if (inb) ring[(hsm + ri) & mask] = (uint16_t)d;
+        __syncthreads();                                          // the step's links, for every lane
+        // ---- search (ndfl_lz_match_kernel's walk) --------------------------------------------------
+        // The walk reads link[rj] for rlo <= rj <= ri only.  Those positions are this stream's, all of
+        // them linked by now (the stream is linked in order, this step included), and none of their
+        // slots has been written again: the newest link is at most 32,768 + 63 past rlo, less than the
+        // ring (or the ring holds the whole stream).  So no link of an earlier stream or an earlier lap
+        // is read; and whatever a link held, a hop is followed only while it stays at or above rlo.
+        const uint32_t maxlen = inb ? min(sp.max_run, len_c - t) : 0u;
+        const int32_t lo_s = max((int32_t)ri - (int32_t)sp.max_dist, 0);
+        const int32_t hi_s = (int32_t)ri - (int32_t)sp.min_dist;
+        const uint32_t rlo = (uint32_t)lo_s, rhi = (uint32_t)hi_s;    // (rhi is used only when hi_s >= lo_s)
+        bool act = inb && t >= pos && maxlen >= sp.min_run && hi_s >= lo_s;   // (positions before pos are inside a run)
+        uint32_t best = 0, bestd = 0, want = 0, rj = ri;
+        // Bound: a pass ends the lane's walk or lowers rj by d >= 1, and rj stays >= rlo >= ri - 32,768:
+        // at most 32,768 passes.  The compare loop adds 4 to k up to maxlen <= 258.
+        while (act) {
+            if (d == 0 || d > rj - rlo) break;
+            rj -= d;
+            d = ring[(hsm + rj) & mask];
+            if (rj > rhi) continue;                               // nearer than min_dist: only the hop
+            const uint32_t x0 = ld4(P, rj, rend) ^ wi0;
+            const uint32_t sbyte = P[rj + best];                  // (rj + best < ri + maxlen <= the chunk's end)
+            if ((x0 & 0xFFFFFFu) == 0 && (best < 3 || sbyte == want)) {   // can be longer
+                uint32_t run;
+                if (x0) run = 3;
+                else {
+                    uint32_t k = 4;
+                    for (;;) {
+                        if (k >= maxlen) { run = maxlen; break; }
+                        const uint32_t y = ld4(P, rj + k, rend) ^ ld4(P, ri + k, rend);
+                        if (y) { run = k + ((uint32_t)__builtin_ctz(y) >> 3); break; }
+                        k += 4;
+                    }
+                }
+                run = min(run, maxlen);
+                if (run > best) {
+                    best = run;
+                    bestd = ri - rj;
+                    if (best >= maxlen) break;
+                    want = P[ri + best];
+                }
+            }
+        }
+        const bool isrun = best >= sp.min_run;
+        const uint32_t m = isrun ? (best << 16 | (bestd - 1)) : (wi0 & 0xFFu);
+        const uint32_t stp = isrun ? best : 1u;
+        // ---- parse: from pos through the step's results (at most 64 hops: each adds >= 1) -----------
+        const uint32_t lim = min(64u, len_c - sb);
+        uint32_t pp = rfl(pos - sb);                              // (pos >= sb: the step before ended at or past it)
+        uint64_t tm = 0;                                          // bit i: a token starts at lane i
+        while (pp < lim) {
+            tm |= 1ull << pp;
+            pp += (uint32_t)__builtin_amdgcn_readlane((int)stp, (int)pp);
+            pp = rfl(pp);
+        }
+        pos = sb + pp;
+        if ((tm >> lane) & 1ull) {
+            toks[ntok + (uint32_t)__builtin_popcountll(tm & ((1ull << lane) - 1ull))] = m;
+            if (dyn) {
+                if (!isrun) atomicAdd(&S.scr.hlit[m], 1u);
+                else {
+                    uint32_t sym, ne, ex;
+                    run_sym(best, sym, ne, ex);
+                    atomicAdd(&S.scr.hlit[sym], 1u);
+                    dist_sym(bestd - 1, sym, ne, ex);
+                    atomicAdd(&S.scr.hdist[sym], 1u);
+                }
+            }
+        }
+        ntok += (uint32_t)__builtin_popcountll(tm);
+    }
+    return ntok;
+}
+
+// The chunk's tokens into the bit buffer, 64 a step.
+__device__ __forceinline__ void emit_tokens(Lds& S, BitOut& bo, const uint32_t* toks, uint32_t ntok) {
+    for (uint32_t i0 = 0; i0 < ntok; i0 += 64) {
+        const int lane = opaque_lane();
+        uint32_t c0 = 0, l0 = 0, ex1 = 0, ne1 = 0, c2 = 0, l2 = 0, ex3 = 0, ne3 = 0;
+        if (i0 + (uint32_t)lane < ntok) {
+            const uint32_t m = toks[i0 + (uint32_t)lane];
+            const uint32_t run = m >> 16;
+            if (!run) {
+                const uint32_t e = S.litCode[m & 0xFFu];
+                c0 = e & 0xFFFFu; l0 = e >> 16;
+            } else {
+                uint32_t sym;
+                run_sym(run, sym, ne1, ex1);
+                const uint32_t e = S.litCode[sym];
+                c0 = e & 0xFFFFu; l0 = e >> 16;
+                dist_sym(m & 0xFFFFu, sym, ne3, ex3);
+                const uint32_t f = S.distCode[sym];
+                c2 = f & 0xFFFFu; l2 = f >> 16;
+            }
+        }
+        const uint32_t mybits = l0 + ne1 + l2 + ne3;              // <= 15 + 5 + 15 + 13
+        const uint32_t incl = wave_incl_scan_l(mybits, lane);
+        const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+        make_room(bo, total);
+        BitPut bp; bp.init(bo.obuf, bo.fill + incl - mybits);
+        bp.put(c0, l0);
+        bp.put(ex1, ne1);
+        bp.put(c2, l2);
+        bp.put(ex3, ne3);
+        bp.flush();
+        bo.fill += total;
+    }
+}
+
+}  // namespace dblz
+
+extern "C" __global__ void __launch_bounds__(64)
+ndfl_deflate_batch_lz_kernel(dblz::Args a) {
+    using namespace dblz;
+    __shared__ __attribute__((aligned(16))) Lds S;
+    // the arguments are needed once per stream or per chunk: parked (dbat::to_v)
+    const uint64_t v_in = to_v((uint64_t)(uintptr_t)a.in), v_out = to_v((uint64_t)(uintptr_t)a.out);
+    const uint64_t v_items = to_v((uint64_t)(uintptr_t)a.items), v_results = to_v((uint64_t)(uintptr_t)a.results);
+    const uint64_t v_ticket = to_v((uint64_t)(uintptr_t)a.ticket), v_tab = to_v((uint64_t)(uintptr_t)a.crc_tab);
+    const uint64_t v_ring = to_v((uint64_t)(uintptr_t)(a.ring + (size_t)blockIdx.x * ((size_t)a.ring_mask + 1)));
+    const uint64_t v_toks = to_v((uint64_t)(uintptr_t)(a.toks + (size_t)blockIdx.x * a.tok_cap));
+    const uint32_t v_mask = to_v(a.ring_mask);
+    const uint32_t v_n = to_v(a.n), v_chunk_len = to_v(a.chunk_len), v_hist = to_v(a.hist_limit);
+    const uint32_t v_dyn = to_v((uint32_t)(a.dynamic != 0));
+    const uint32_t v_minr = to_v(a.min_run), v_maxr = to_v(a.max_run), v_mind = to_v(a.min_dist), v_maxd = to_v(a.max_dist);
+    for (;;) {
+        __syncthreads();
+        if (opaque_lane() == 0) S.ticket = atomicAdd((uint32_t*)(uintptr_t)to_s(v_ticket), 1u);
+        __syncthreads();
+        const uint32_t v_si = to_v(S.ticket);
+        if (to_s(v_si) >= to_s(v_n)) break;
+        // the stream's constants, parked too
+        uint64_t v_src, v_len;
+        uint32_t v_fmt, v_kind;
+        BitOut bo{S.obuf, 0ull, 0ull, to_v((uint64_t)0), 0u};
+        {
+            const ndfl_member_item it = ((const ndfl_member_item*)(uintptr_t)to_s(v_items))[to_s(v_si)];
+            v_src = to_v(to_s(v_in) + it.in_off); v_len = to_v(it.in_len);
+            bo.v_optr = to_v(to_s(v_out) + it.out_off); bo.v_cap = to_v(it.out_cap);
+            v_fmt = to_v(it.format);
+            v_kind = to_v(it.format == NDFL_FMT_ZLIB ? NDFL_SUM_ADLER32 : it.format == NDFL_FMT_GZIP ? NDFL_SUM_CRC32 : it.sum);
+        }
+        // the running state, all of it started afresh for the stream: checksum, bit buffer, head table and
+        // its base (the ring needs no clearing: lz_chunk reads only links this stream has written)
+        uint32_t v_ck, v_fill = to_v(0u), v_cb = to_v(0u);
+        uint64_t v_cs = to_v((uint64_t)0);
+        {
+            const uint32_t kind = to_s(v_kind);
+            v_ck = to_v(kind == NDFL_SUM_CRC32 ? 0xFFFFFFFFu : kind == NDFL_SUM_ADLER32 ? 1u : 0u);
+        }
+        for (uint32_t j = (uint32_t)opaque_lane(); j <= OBW; j += 64) S.obuf[j] = 0;
+        for (uint32_t j = (uint32_t)opaque_lane(); j < NHEAD / 2; j += 64) ((uint32_t*)S.head)[j] = HNONE << 16 | HNONE;
+        for (;;) {
+            if (to_s(v_dyn)) {
+                const int lane = opaque_lane();
+                for (int t = lane; t < 288; t += 64) S.scr.hlit[t] = 0;
+                if (lane < 32) S.scr.hdist[lane] = 0;
+            }
+            __syncthreads();
+            uint32_t v_ntok;
+            {
+                const uint64_t cs = to_s(v_cs), len = to_s(v_len);
+                const uint32_t len_c = (uint32_t)min((uint64_t)to_s(v_chunk_len), len - cs);
+                const uint64_t hs = cs - min((uint64_t)to_s(v_hist), cs);      // chunk 0 has no history
+                const uint8_t* P = (const uint8_t*)(uintptr_t)(to_s(v_src) + hs);
+                const uint32_t rc0 = (uint32_t)(cs - hs);
+                const uint32_t rend = (uint32_t)min(len - hs, (uint64_t)rc0 + len_c + 8);
+                uint32_t ck = to_s(v_ck);
+                fold_chunk(v_tab, P + rc0, len_c, to_s(v_kind), ck);
+                v_ck = to_v(ck);
+                const Search sp{to_s(v_minr), to_s(v_maxr), to_s(v_mind), to_s(v_maxd)};
+                uint32_t cb = to_s(v_cb);
+                v_ntok = to_v(lz_chunk(S, sp, P, rc0, len_c, rend, (uint32_t)hs, (uint16_t*)(uintptr_t)to_s(v_ring),
+                                       to_s(v_mask), (uint32_t*)(uintptr_t)to_s(v_toks), to_s(v_dyn) != 0, cb));
+                v_cb = to_v(cb + len_c);
+                if (to_s(v_dyn) && opaque_lane() == 0) {
+                    atomicAdd(&S.scr.hlit[256], 1u);                  // end of block (:131-132)
+                    if (len_c == 0) atomicAdd(&S.scr.hlit[0], 1u);    // (:146-147)
+                }
+            }
+            __syncthreads();                                          // the histograms and the token list
+            uint32_t hb;
+            {
+                const uint64_t len = to_s(v_len), cs = to_s(v_cs);
+                const bool is_final = len - cs <= (uint64_t)to_s(v_chunk_len);
+                hb = build_block_codes<64, true>(S.scr, to_s(v_dyn) != 0, is_final, S.litCode, S.distCode);
+            }
+            bo.fill = to_s(v_fill);
+            // the header (S.scr.hdr(), zero past its bits) into the bit buffer
+            make_room(bo, hb);
+            for (uint32_t k = (uint32_t)opaque_lane(); 32 * k < hb; k += 64) {
+                const uint32_t nbk = min(32u, hb - 32 * k), word = S.scr.hdr()[k];
+                BitPut bp; bp.init(bo.obuf, bo.fill + 32 * k);
+                bp.put(word & 0xFFFF, min(nbk, 16u));
+                if (nbk > 16) bp.put(word >> 16, nbk - 16);
+                bp.flush();
+            }
+            bo.fill += hb;
+            emit_tokens(S, bo, (const uint32_t*)(uintptr_t)to_s(v_toks), to_s(v_ntok));
+            {
+                const uint64_t cs = to_s(v_cs);
+                v_cs = to_v(cs + min((uint64_t)to_s(v_chunk_len), to_s(v_len) - cs));
+            }
+            // the end-of-block code (D/comp/Lz77Huffman.java:285)
+            const uint32_t eob = rfl(S.litCode[256]);
+            make_room(bo, eob >> 16);
+            if (opaque_lane() == 0) put_end_of_block(bo.obuf, bo.fill, eob);
+            bo.fill += eob >> 16;
+            v_fill = to_v(bo.fill);
+            if (to_s(v_cs) >= to_s(v_len)) break;
+        }
+        // finish(): pad to a byte (zero bits), then the container's trailer (as ndfl_deflate_batch_kernel)
+        bo.fill = to_s(v_fill);
+        const uint64_t v_end_bits = to_v(to_s(bo.v_wbase) * 8 + bo.fill);
+        const uint32_t fmt = to_s(v_fmt);
+        const uint32_t sum = to_s(v_kind) == NDFL_SUM_CRC32 ? ~to_s(v_ck) : to_s(v_ck);
+        const uint32_t tl = fmt == NDFL_FMT_ZLIB ? 4u : fmt == NDFL_FMT_GZIP ? 8u : 0u;
+        make_room(bo, 7 + 64);
+        bo.fill = (bo.fill + 7) & ~7u;
+        const int lane = opaque_lane();
+        if (lane == 0 && tl) {
+            BitPut bp; bp.init(bo.obuf, bo.fill);
+            if (fmt == NDFL_FMT_ZLIB) {                               // big-endian Adler-32
+                for (int k = 3; k >= 0; k--) bp.put((sum >> (8 * k)) & 0xFFu, 8);
+            } else {                                                  // CRC-32, ISIZE: little-endian
+                const uint32_t isz = (uint32_t)v_len;
+                for (int k = 0; k < 4; k++) bp.put((sum >> (8 * k)) & 0xFFu, 8);
+                for (int k = 0; k < 4; k++) bp.put((isz >> (8 * k)) & 0xFFu, 8);
+            }
+            bp.flush();
+        }
+        bo.fill += 8 * tl;
+        __syncthreads();
+        store_bytes(bo, bo.fill >> 3);
+        if (lane == 0) {
+            ndfl_deflate_result rr;
+            rr.out_len = bo.v_wbase + (bo.fill >> 3);
+            rr.status = rr.out_len > bo.v_cap ? NDFL_E_CAPACITY : 0;
+            rr.checksum = sum;
+            rr.end_bits = v_end_bits;
+            ((ndfl_deflate_result*)(uintptr_t)v_results)[v_si] = rr;
+        }
+    }
+}
+
+// ---- host side ------------------------------------------------------------------------------------
+// The link rings and token lists of the grid's waves: grown on demand, kept by the context.
+struct BatchLzScratch {
+    void* d_mem = nullptr; size_t d_mem_cap = 0;
+    void release() {
+        if (d_mem) hipFree(d_mem);
+        d_mem = nullptr;
+        d_mem_cap = 0;
+    }
+};
+
+// The most device memory the rings and token lists may take; the grid is lowered to fit.  A wave needs
+// at most 128 KiB of links and 256 KiB of tokens, so the budget never leaves fewer than 682 waves.
+constexpr size_t BATCH_LZ_BUDGET = (size_t)256 << 20;
+
+// deflate_batch_run's launcher for ndfl_deflate_batch_lz_kernel: sizes the wave's ring and token list from
+// the batch, lowers the grid to the budget, grows the scratch (first use only) and launches.
+struct BatchLzLaunch {
+    BatchLzScratch& Z;
+    const Knobs& knobs;
+    const ndfl_member_item* items;       // host
+    uint32_t n;
+    dblz::Args a;                         // the search parameters, chunk_len, hist_limit, dynamic, crc_tab
+    int operator()(hipStream_t s, const uint8_t* d_src, uint8_t* d_out, const ndfl_member_item* d_items,
+                   ndfl_deflate_result* d_res, uint32_t* d_ticket, hipEvent_t e0, hipEvent_t e1) {
+        uint64_t longest = 0;
+        for (uint32_t i = 0; i < n; i++) longest = std::max(longest, items[i].in_len);
+        uint32_t ring = 64;
+        while (ring < dblz::RING_MAX && ring < longest) ring <<= 1;
+        const uint32_t tok_cap = (uint32_t)std::max<uint64_t>(64, std::min<uint64_t>(a.chunk_len, longest));
+        const size_t per_wave = (size_t)ring * 2 + (size_t)tok_cap * 4;
+        static const uint32_t auto_grid = wave_grid(ndfl_deflate_batch_lz_kernel, 256 * 16);
+        uint32_t grid = std::min(n, auto_grid);
+        if (knobs.batch_waves) grid = std::min(grid, knobs.batch_waves);
+        grid = (uint32_t)std::max<size_t>(1, std::min<size_t>(grid, BATCH_LZ_BUDGET / per_wave));
+        if (knobs.stats)
+            fprintf(stderr, "[ndfl] deflate batch lz77: %u streams, %u waves (of %u), %zu scratch bytes per wave\n", n, grid,
+                    auto_grid, per_wave);
+        INF_CHK(inf_ensure(&Z.d_mem, &Z.d_mem_cap, (size_t)grid * per_wave));
+        a.in = d_src; a.out = d_out; a.items = d_items; a.results = d_res; a.n = n; a.ticket = d_ticket;
+        a.toks = (uint32_t*)Z.d_mem; a.tok_cap = tok_cap;
+        a.ring = (uint16_t*)((char*)Z.d_mem + (size_t)grid * tok_cap * 4); a.ring_mask = ring - 1;
+        INF_CHK(hipEventRecord(e0, s));
+        hipLaunchKernelGGL(ndfl_deflate_batch_lz_kernel, dim3(grid), dim3(64), 0, s, a);
+        INF_CHK(hipGetLastError());
+        INF_CHK(hipEventRecord(e1, s));
+        return 0;
+    }
+};

@@ -466,6 +466,21 @@ class Context:
                                    chunk_len, hist_limit, flags), "ndfl_deflate_batch")
         return [(r.status, r.checksum, r.out_len, r.end_bits) for r in res[:n]]
 
+    def deflate_batch_lz77_raw(self, in_addr, in_size, out_addr, out_size, items, dynamic, min_run, max_run, min_dist,
+                               max_dist, chunk_len, hist_limit, flags):
+        """ndfl_deflate_batch_lz77: deflate_batch_raw with Lz77Huffman(dynamic, min_run, max_run, min_dist,
+        max_dist) as the strategy; the same items and the same (status, checksum, out_len, end_bits) per
+        stream."""
+        L = load()
+        self._order()
+        n = len(items)
+        arr = (_lib.MemberItem * max(1, n))(*[_lib.MemberItem(*map(int, it)) for it in items])
+        res = (_lib.DeflateResult * max(1, n))()
+        check(L.ndfl_deflate_batch_lz77(self._h, in_addr, in_size, out_addr, out_size, arr, res, n, int(dynamic),
+                                        min_run, max_run, min_dist, max_dist, chunk_len, hist_limit, flags),
+              "ndfl_deflate_batch_lz77")
+        return [(r.status, r.checksum, r.out_len, r.end_bits) for r in res[:n]]
+
     def _deflate_packed(self, buffers, fmt, kind, headers, strategy, chunk_len, hist_limit):
         """One batch over host buffers: each region is its header's bytes (the caller's part of a
         container) followed by room for ndfl_deflate_bound(len) bytes and the trailer.  Returns one
@@ -476,7 +491,7 @@ class Context:
         src = ctypes.create_string_buffer(packed, max(1, len(packed)))
         items, regions, in_off, out_off = [], [], 0, 0
         for b, h in zip(buffers, headers):
-            cap = L.ndfl_deflate_bound(len(b), chunk_len) + 8
+            cap = L.ndfl_deflate_bound(len(b), chunk_len) * (2 if isinstance(strategy, Lz77Huffman) else 1) + 8
             items.append((in_off, len(b), out_off + len(h), cap, fmt, kind))
             regions.append(out_off)
             in_off += len(b)
@@ -484,8 +499,12 @@ class Context:
         out = ctypes.create_string_buffer(max(1, out_off))
         for at, h in zip(regions, headers):
             ctypes.memmove(ctypes.addressof(out) + at, bytes(h), len(h))
-        res = self.deflate_batch_raw(ctypes.addressof(src), len(packed), ctypes.addressof(out), out_off, items,
-                                     strategy, chunk_len, hist_limit, 0)
+        if isinstance(strategy, Lz77Huffman):        # (a preset's name or id keeps ndfl_deflate_batch)
+            res = self.deflate_batch_lz77_raw(ctypes.addressof(src), len(packed), ctypes.addressof(out), out_off, items,
+                                              strategy.useDynamicHuffmanCodes, *strategy.params, chunk_len, hist_limit, 0)
+        else:
+            res = self.deflate_batch_raw(ctypes.addressof(src), len(packed), ctypes.addressof(out), out_off, items,
+                                         strategy, chunk_len, hist_limit, 0)
         done = []
         for at, h, r in zip(regions, headers, res):
             status, checksum, olen, end_bits = r
@@ -495,7 +514,8 @@ class Context:
 
     def deflate_batch(self, buffers, strategy=Strategy.RLE_DYNAMIC, chunk_len=65536, hist_limit=32768, sum=None):
         """Compress many independent host buffers in one call, each as deflate() compresses it alone
-        (RLE_* / LITERAL_* presets).  Returns one (bytes, end_bits, checksum) per buffer; checksum is
+        (RLE_* / LITERAL_* presets by name or id through ndfl_deflate_batch; an Lz77Huffman instance, FULL_*
+        among them, through ndfl_deflate_batch_lz77).  Returns one (bytes, end_bits, checksum) per buffer; checksum is
         the buffer's CRC-32 / Adler-32 with sum = SUM_CRC32 / SUM_ADLER32, else 0."""
         buffers = list(buffers)
         kind = _lib.SUM_NONE if sum is None else int(sum)
@@ -506,7 +526,7 @@ class Context:
         """Compress many independent host buffers into complete zlib (FMT_ZLIB) or gzip (FMT_GZIP)
         members in one call: what ZlibOutputStream / GzipOutputStream write for each buffer alone.  The
         header is `meta`'s (a ZlibMetadata / GzipMetadata; default ZlibMetadata.DEFAULT / GzipMetadata()),
-        the trailer the kernel's.  Returns one bytes object per buffer."""
+        the trailer the kernel's; `strategy` as for deflate_batch.  Returns one bytes object per buffer."""
         from .streams import GzipMetadata, ZlibMetadata
         buffers = list(buffers)
         fmt = int(format)

@@ -403,6 +403,48 @@ int ndfl_deflate_batch(ndfl_ctx* ctx, const uint8_t* in, uint64_t in_size, uint8
                        int strategy, uint32_t chunk_len, uint32_t hist_limit, uint32_t flags);
 
 /*
+ * ndfl_deflate_batch with the LZ77 search: stream i is DeflaterOutputStream(out, chunk_len, hist_limit,
+ * Lz77Huffman(dynamic, min_run, max_run, min_dist, max_dist)): write all bytes, then finish().  Still one
+ * kernel launch and one host sync whatever n is (ndfl_deflate_chunks_lz77 costs three kernels of 1024-thread
+ * workgroups and a sync per buffer).  Items, results, formats, `sum`, trailers, NDFL_E_CAPACITY with the
+ * required size, the rule that no byte of `out` outside [out_off, out_off + min(out_len, out_cap)) is
+ * written, flags, stream ordering, ndfl_ctx_last_kernel_ms, n == 0, overlapping or repeated input regions
+ * and the argument errors are ndfl_deflate_batch's, word for word.
+ *   dynamic, min_run, max_run, min_dist, max_dist
+ *               as ndfl_deflate_chunks_lz77: (0, 0, 0, 0) is the literal-only form, anything else outside
+ *               3 <= min_run <= max_run <= 258, 1 <= min_dist <= max_dist <= 32768 is NDFL_E_ARG;
+ *               (3, 258, 1, 32768) is FULL_STATIC / FULL_DYNAMIC.  The literal-only and the (3, 258, 1, 1)
+ *               forms run as ndfl_deflate_batch's LITERAL_* and RLE_* presets.
+ *   chunk_len   1..65536 (0: NDFL_E_ARG; above 65536: NDFL_E_UNSUPPORTED)
+ *   hist_limit  0..32768, else NDFL_E_ARG
+ * A stream's DEFLATE bytes and end_bits are bit-identical to ndfl_deflate_chunks_lz77(ctx, NULL, 0,
+ * hist_limit, data_i, len_i, chunk_len, ..., 1, 0, ...).  Chunk 0 has no history; a chunk that starts at
+ * stream offset cs has the min(hist_limit, cs) bytes before it, the stream's own and never a neighbour's,
+ * whatever lies next to it in `in`.  At position q the candidates are the distances min_dist ..
+ * min(max_dist, q - (cs - min(hist_limit, cs))); a run is capped at max_run and at the chunk's end; the
+ * longest run wins, the smallest distance among equal runs (D/comp/Lz77Huffman.java:68-90); a run below
+ * min_run is a literal.
+ * One wave encodes a stream, and keeps its hash-chain links and its chunk's tokens in device memory the
+ * context owns: at most 384 KiB per wave, sized from the batch's longest in_len and chunk_len, grown on
+ * first use, and never more than 256 MiB (the grid is lowered to fit).
+ * Crossover to a loop of ndfl_deflate_chunks_lz77 calls (measured on one MI355X, FULL_DYNAMIC with a CRC-32,
+ * DESIGN.md §4 "Batched LZ77 deflate"): the loop costs 0.42 to 0.63 ms per buffer up to 1 MiB, nearly all of it
+ * per-call cost; the batch costs about 0.1 ms per call, a wave about 0.08 ms per stream plus 0.12 ms per KiB
+ * while the stream is a few KiB, 0.6 ms per KiB (1.7 MB/s) once its window is full, and up to 1,792 waves run
+ * at once.  65,536 x 512 B take 5.8 to 7.3 ms in a batch and 27 to 33 s in a loop, 4,096 x 4 KiB 1.8 to 3.4 ms
+ * and 1.8 to 2.2 s; 256 x 1 MiB take 625 to 808 ms in a batch and 133 to 162 ms in a loop: the batch loses
+ * there.  So one buffer alone is faster here below about 2.5 KB, ten below about 8 KB each, a hundred below about
+ * 80 KB, 256 below about 220 KB; larger buffers, which ndfl_deflate_chunks_lz77 searches with whole workgroups
+ * and the window in LDS, belong there whatever the count.  Against ndfl_deflate_batch's RLE_DYNAMIC the kernel
+ * takes 2.5 to 7 times as long on these small buffers, and 4 KiB text buffers come out at 56 % of their size
+ * instead of 99 %.
+ */
+int ndfl_deflate_batch_lz77(ndfl_ctx* ctx, const uint8_t* in, uint64_t in_size, uint8_t* out, uint64_t out_size,
+                            const ndfl_member_item* items, ndfl_deflate_result* results, uint32_t n,
+                            int dynamic, int min_run, int max_run, int min_dist, int max_dist,
+                            uint32_t chunk_len, uint32_t hist_limit, uint32_t flags);
+
+/*
  * Decompress the block-aligned bit range [start_bit, end_bit) of one raw DEFLATE stream: one GPU's
  * shard of a stream decoded across GPUs, or one batch of a stream read incrementally
  * (NDFL_IN_PARTIAL, end_bit UINT64_MAX: InflaterInputStream's bounded input buffer,

@@ -24,7 +24,11 @@ without ndfl_inflate_members.
 
 The encoder's side (--mode deflate | deflate-loop, --data text | runs; see deflate_modes): one
 ndfl_deflate_batch call against one ndfl_deflate_chunks call per buffer, RLE_DYNAMIC with the CRC-32
-of each buffer, on the same three shapes; the lines are "bench": "batch_deflate".
+of each buffer, on the same three shapes; the lines are "bench": "batch_deflate".  With the LZ77 search
+(--mode deflate-lz | deflate-lz-loop): one ndfl_deflate_batch_lz77 call against one
+ndfl_deflate_chunks_lz77 call per buffer, FULL_DYNAMIC, everything else the same; the lines are "bench":
+"batch_deflate_lz".  The four modes may share one run (--mode deflate,deflate-lz: both batch kernels on
+the same buffers, their kernel times and compressed sizes side by side).
 """
 import argparse
 import ctypes
@@ -101,7 +105,9 @@ def make_buffers(name, seed, kind):
 def deflate_modes(a, modes):
     """--mode deflate: one ndfl_deflate_batch call (raw DEFLATE with the CRC-32 of each buffer);
     --mode deflate-loop: one ndfl_deflate_chunks call per buffer with crc_inout, which also runs on a
-    build without the batch entry point (NDFL_LIB_PATH): the baseline.  Input and output are
+    build without the batch entry point (NDFL_LIB_PATH): the baseline.  --mode deflate-lz and
+    deflate-lz-loop: the same with ndfl_deflate_batch_lz77 and ndfl_deflate_chunks_lz77, FULL_DYNAMIC
+    (the loop again runs on a build without the batch entry point).  Input and output are
     device-resident; every buffer and every output region starts 16-byte aligned, and a region holds
     ndfl_deflate_bound bytes, so the loop's encoder writes it in place.  The first pass decodes every
     region with ndfl_inflate_members (raw + CRC-32) and compares the bytes and the checksums."""
@@ -112,6 +118,7 @@ def deflate_modes(a, modes):
     L = ndfl._lib.load()
     flags = ndfl.IN_DEVICE | ndfl.OUT_DEVICE
     strategy = ndfl._lib.STRATEGIES["RLE_DYNAMIC"]
+    full_dynamic = (1, 3, 258, 1, 32768)             # Lz77Huffman.FULL_DYNAMIC
     chunk_len, hist_limit = 65536, 32768
     u64, u32 = ctypes.c_uint64, ctypes.c_uint32
     for name in a.shapes.split(","):
@@ -130,22 +137,32 @@ def deflate_modes(a, modes):
         pi, po = d_in.data_ptr(), d_out.data_ptr()
         for mode in modes:
             out_lens, sums = [0] * n, [0] * n
-            if mode == "deflate":
+            batch, lz = mode in ("deflate", "deflate-lz"), mode in ("deflate-lz", "deflate-lz-loop")
+            if batch:
                 arr = (ndfl._lib.MemberItem * n)(*[ndfl._lib.MemberItem(i * in_stride, size, i * cap, cap, ndfl._lib.FMT_RAW,
                                                                         ndfl._lib.SUM_CRC32) for i in range(n)])
                 res = (ndfl._lib.DeflateResult * n)()
 
             def once():
-                if mode == "deflate":
-                    rc = L.ndfl_deflate_batch(ctx._h, pi, n * in_stride, po, n * cap, arr, res, n, strategy, chunk_len,
-                                              hist_limit, flags)
+                if batch:
+                    if lz:
+                        rc = L.ndfl_deflate_batch_lz77(ctx._h, pi, n * in_stride, po, n * cap, arr, res, n, *full_dynamic,
+                                                       chunk_len, hist_limit, flags)
+                    else:
+                        rc = L.ndfl_deflate_batch(ctx._h, pi, n * in_stride, po, n * cap, arr, res, n, strategy, chunk_len,
+                                                  hist_limit, flags)
                     assert rc == 0, rc
                     return ctx.last_kernel_ms()
                 bits, crc = u64(0), u32(0)
                 for i in range(n):
                     crc.value = 0
-                    rc = L.ndfl_deflate_chunks(ctx._h, None, 0, hist_limit, pi + i * in_stride, size, chunk_len, strategy, 1,
-                                               0, po + i * cap, cap, ctypes.byref(bits), ctypes.byref(crc), flags)
+                    if lz:
+                        rc = L.ndfl_deflate_chunks_lz77(ctx._h, None, 0, hist_limit, pi + i * in_stride, size, chunk_len,
+                                                        *full_dynamic, 1, 0, po + i * cap, cap, ctypes.byref(bits),
+                                                        ctypes.byref(crc), flags)
+                    else:
+                        rc = L.ndfl_deflate_chunks(ctx._h, None, 0, hist_limit, pi + i * in_stride, size, chunk_len, strategy,
+                                                   1, 0, po + i * cap, cap, ctypes.byref(bits), ctypes.byref(crc), flags)
                     assert rc == 0, rc
                     out_lens[i] = (bits.value + 7) // 8
                     sums[i] = crc.value
@@ -160,7 +177,7 @@ def deflate_modes(a, modes):
                 torch.cuda.synchronize()
                 dt = (time.perf_counter() - t0) * 1e3
                 if it == 0:
-                    if mode == "deflate":
+                    if batch:
                         assert all(r.status == 0 for r in res)
                         out_lens, sums = [r.out_len for r in res], [r.checksum for r in res]
                     assert sums == crcs, "checksums differ"
@@ -172,8 +189,9 @@ def deflate_modes(a, modes):
                 if it >= a.warmup:
                     times.append(dt)
             med = statistics.median(times)
-            line = {"bench": "batch_deflate", "label": a.label, "mode": mode, "data": a.data, "shape": name, "buffers": n,
-                    "buffer_bytes": size, "in_bytes": n * size, "out_bytes": sum(out_lens), "strategy": "RLE_DYNAMIC",
+            line = {"bench": "batch_deflate_lz" if lz else "batch_deflate", "label": a.label, "mode": mode, "data": a.data,
+                    "shape": name, "buffers": n, "buffer_bytes": size, "in_bytes": n * size, "out_bytes": sum(out_lens),
+                    "strategy": "FULL_DYNAMIC" if lz else "RLE_DYNAMIC",
                     "ms_median": round(med, 3), "ms_all": [round(t, 3) for t in times],
                     "in_MBps": round(n * size / med / 1e3, 1)}
             if kms is not None:
@@ -185,7 +203,8 @@ def deflate_modes(a, modes):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", required=True,
-                    help="comma-separated: loop, batch, members, batch+sum; or deflate, deflate-loop")
+                    help="comma-separated: loop, batch, members, batch+sum; or deflate, deflate-loop, deflate-lz, "
+                         "deflate-lz-loop")
     ap.add_argument("--data", choices=["text", "runs"], default="text", help="deflate modes: the buffers' content")
     ap.add_argument("--format", choices=["zlib", "gzip", "raw-crc"], default="zlib",
                     help="members / batch+sum: the container of each stream")
@@ -195,7 +214,7 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--label", default="")
     a = ap.parse_args()
-    if all(m in ("deflate", "deflate-loop") for m in a.mode.split(",")):
+    if all(m in ("deflate", "deflate-loop", "deflate-lz", "deflate-lz-loop") for m in a.mode.split(",")):
         return deflate_modes(a, a.mode.split(","))
     import torch
     import ndfl
