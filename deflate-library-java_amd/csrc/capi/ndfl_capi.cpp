@@ -1049,6 +1049,28 @@ static void batch_public_reasons(Result* results, uint32_t n) {
     }
 }
 
+// The per-item rule of the calls that take ndfl_member_item: a known format and checksum kind.
+static bool member_items_valid(const ndfl_member_item* items, uint32_t n) {
+    for (uint32_t i = 0; i < n; i++)
+        if (items[i].format > NDFL_FMT_GZIP || items[i].sum > NDFL_SUM_ADLER32) return false;
+    return true;
+}
+
+// What the two batched deflate calls check after their strategy, in this order: chunk_len and
+// hist_limit, the call-level rules, the items.
+static int deflate_batch_args(const uint8_t* in, uint64_t in_size, const uint8_t* out, uint64_t out_size,
+                              const ndfl_member_item* items, const void* results, uint32_t n, uint32_t chunk_len,
+                              uint32_t hist_limit) {
+    if (chunk_len == 0 || hist_limit > 32768) return NDFL_E_ARG;
+    if (chunk_len > (uint32_t)MAX_CHUNK) return NDFL_E_UNSUPPORTED;
+    if (!batch_regions_valid(in, in_size, out, out_size, items, results, n) || !member_items_valid(items, n))
+        return NDFL_E_ARG;
+    return NDFL_OK;
+}
+
+// A batch runner's return code as the C ABI's.
+static int batch_status(int r) { return !r ? NDFL_OK : r == -4 ? NDFL_E_DEVICE : NDFL_E_INTERNAL; }
+
 extern "C" {
 
 int ndfl_inflate_batch(ndfl_ctx* c, const uint8_t* in, uint64_t in_size, uint8_t* out, uint64_t out_size,
@@ -1057,26 +1079,24 @@ int ndfl_inflate_batch(ndfl_ctx* c, const uint8_t* in, uint64_t in_size, uint8_t
     if (n == 0) return NDFL_OK;
     if (!batch_regions_valid(in, in_size, out, out_size, items, results, n)) return NDFL_E_ARG;
     HIPCHK(hipSetDevice(c->device));
-    const int r = inflate_batch_run<false>(c->inf, c->batch, ordered_stream(c), c->ev0, c->ev1, in, in_size, out, items,
-                                           results, n, flags, &c->last_ms);
-    if (r) return r == -4 ? NDFL_E_DEVICE : NDFL_E_INTERNAL;
-    batch_public_reasons(results, n);
-    return NDFL_OK;
+    const int r = batch_status(inflate_batch_run<false>(c->inf, c->batch, ordered_stream(c), c->ev0, c->ev1, in, in_size, out,
+                                                        items, results, n, flags, &c->last_ms));
+    if (r == NDFL_OK) batch_public_reasons(results, n);
+    return r;
 }
 
 int ndfl_inflate_members(ndfl_ctx* c, const uint8_t* in, uint64_t in_size, uint8_t* out, uint64_t out_size,
                          const ndfl_member_item* items, ndfl_member_result* results, uint32_t n, uint32_t flags) {
     if (!c) return NDFL_E_ARG;
     if (n == 0) return NDFL_OK;
-    if (!batch_regions_valid(in, in_size, out, out_size, items, results, n)) return NDFL_E_ARG;
-    for (uint32_t i = 0; i < n; i++)
-        if (items[i].format > NDFL_FMT_GZIP || items[i].sum > NDFL_SUM_ADLER32) return NDFL_E_ARG;
+    if (!batch_regions_valid(in, in_size, out, out_size, items, results, n) || !member_items_valid(items, n))
+        return NDFL_E_ARG;
     HIPCHK(hipSetDevice(c->device));
-    const int r = inflate_batch_run<true>(c->inf, c->batch, ordered_stream(c), c->ev0, c->ev1, in, in_size, out, items,
-                                          results, n, flags, &c->last_ms, c->d_tabs.as<uint32_t>() + 1024);
-    if (r) return r == -4 ? NDFL_E_DEVICE : NDFL_E_INTERNAL;
-    batch_public_reasons(results, n);
-    return NDFL_OK;
+    const int r = batch_status(inflate_batch_run<true>(c->inf, c->batch, ordered_stream(c), c->ev0, c->ev1, in, in_size, out,
+                                                       items, results, n, flags, &c->last_ms,
+                                                       c->d_tabs.as<uint32_t>() + 1024));
+    if (r == NDFL_OK) batch_public_reasons(results, n);
+    return r;
 }
 
 int ndfl_deflate_batch(ndfl_ctx* c, const uint8_t* in, uint64_t in_size, uint8_t* out, uint64_t out_size,
@@ -1084,27 +1104,21 @@ int ndfl_deflate_batch(ndfl_ctx* c, const uint8_t* in, uint64_t in_size, uint8_t
                        uint32_t chunk_len, uint32_t hist_limit, uint32_t flags) {
     if (!c) return NDFL_E_ARG;
     if (n == 0) return NDFL_OK;
-    int rle, dyn;
+    BatchRleLaunch launch{c->knobs, dbat::Args{}};
     switch (strategy) {
-        case NDFL_LITERAL_STATIC: rle = 0; dyn = 0; break;
-        case NDFL_LITERAL_DYNAMIC: rle = 0; dyn = 1; break;
-        case NDFL_RLE_STATIC: rle = 1; dyn = 0; break;
-        case NDFL_RLE_DYNAMIC: rle = 1; dyn = 1; break;
+        case NDFL_LITERAL_STATIC: launch.a.rle = 0; launch.a.dynamic = 0; break;
+        case NDFL_LITERAL_DYNAMIC: launch.a.rle = 0; launch.a.dynamic = 1; break;
+        case NDFL_RLE_STATIC: launch.a.rle = 1; launch.a.dynamic = 0; break;
+        case NDFL_RLE_DYNAMIC: launch.a.rle = 1; launch.a.dynamic = 1; break;
         case NDFL_FULL_STATIC: case NDFL_FULL_DYNAMIC: case NDFL_UNCOMPRESSED: return NDFL_E_UNSUPPORTED;
         default: return NDFL_E_ARG;
     }
-    if (chunk_len == 0 || hist_limit > 32768) return NDFL_E_ARG;
-    if (chunk_len > (uint32_t)MAX_CHUNK) return NDFL_E_UNSUPPORTED;
-    if (!batch_regions_valid(in, in_size, out, out_size, items, results, n)) return NDFL_E_ARG;
-    for (uint32_t i = 0; i < n; i++)
-        if (items[i].format > NDFL_FMT_GZIP || items[i].sum > NDFL_SUM_ADLER32) return NDFL_E_ARG;
+    if (const int e = deflate_batch_args(in, in_size, out, out_size, items, results, n, chunk_len, hist_limit)) return e;
     HIPCHK(hipSetDevice(c->device));
-    const int r = deflate_batch_run(c->batch, &c->d_in.p, &c->d_in.cap, ordered_stream(c), c->ev0, c->ev1, in, out, items,
-                                    results, n, flags,
-                                    BatchRleLaunch{c->knobs, n, rle, dyn, chunk_len, hist_limit, c->d_tabs.as<uint32_t>()},
-                                    &c->last_ms);
-    if (r) return r == -4 ? NDFL_E_DEVICE : NDFL_E_INTERNAL;
-    return NDFL_OK;
+    launch.a.n = n; launch.a.chunk_len = chunk_len; launch.a.hist_enabled = hist_limit > 0;
+    launch.a.crc_tab = c->d_tabs.as<uint32_t>(); launch.a.crc_x = launch.a.crc_tab + 1024;
+    return batch_status(deflate_batch_run(c->batch, &c->d_in.p, &c->d_in.cap, ordered_stream(c), c->ev0, c->ev1, in, out,
+                                          items, results, n, flags, launch, &c->last_ms));
 }
 
 int ndfl_deflate_batch_lz77(ndfl_ctx* c, const uint8_t* in, uint64_t in_size, uint8_t* out, uint64_t out_size,
@@ -1123,21 +1137,15 @@ int ndfl_deflate_batch_lz77(ndfl_ctx* c, const uint8_t* in, uint64_t in_size, ui
                                   literal_only ? (dynamic ? NDFL_LITERAL_DYNAMIC : NDFL_LITERAL_STATIC)
                                                : (dynamic ? NDFL_RLE_DYNAMIC : NDFL_RLE_STATIC),
                                   chunk_len, hist_limit, flags);
-    if (chunk_len == 0 || hist_limit > 32768) return NDFL_E_ARG;
-    if (chunk_len > (uint32_t)MAX_CHUNK) return NDFL_E_UNSUPPORTED;
-    if (!batch_regions_valid(in, in_size, out, out_size, items, results, n)) return NDFL_E_ARG;
-    for (uint32_t i = 0; i < n; i++)
-        if (items[i].format > NDFL_FMT_GZIP || items[i].sum > NDFL_SUM_ADLER32) return NDFL_E_ARG;
+    if (const int e = deflate_batch_args(in, in_size, out, out_size, items, results, n, chunk_len, hist_limit)) return e;
     HIPCHK(hipSetDevice(c->device));
-    BatchLzLaunch launch{c->batch_lz, c->knobs, items, n, dblz::Args{}};
-    launch.a.chunk_len = chunk_len; launch.a.hist_limit = hist_limit; launch.a.dynamic = dynamic != 0;
+    BatchLzLaunch launch{c->batch_lz, c->knobs, items, dblz::Args{}};
+    launch.a.n = n; launch.a.chunk_len = chunk_len; launch.a.hist_limit = hist_limit; launch.a.dynamic = dynamic != 0;
     launch.a.min_run = (uint32_t)min_run; launch.a.max_run = (uint32_t)max_run;
     launch.a.min_dist = (uint32_t)min_dist; launch.a.max_dist = (uint32_t)max_dist;
     launch.a.crc_tab = c->d_tabs.as<uint32_t>();
-    const int r = deflate_batch_run(c->batch, &c->d_in.p, &c->d_in.cap, ordered_stream(c), c->ev0, c->ev1, in, out, items,
-                                    results, n, flags, launch, &c->last_ms);
-    if (r) return r == -4 ? NDFL_E_DEVICE : NDFL_E_INTERNAL;
-    return NDFL_OK;
+    return batch_status(deflate_batch_run(c->batch, &c->d_in.p, &c->d_in.cap, ordered_stream(c), c->ev0, c->ev1, in, out,
+                                          items, results, n, flags, launch, &c->last_ms));
 }
 
 int ndfl_inflate_range(ndfl_ctx* c, const uint8_t* in, uint64_t in_len, uint64_t start_bit, uint64_t end_bit,

@@ -54,7 +54,8 @@ static_assert(31 + 15 * STEP <= 32 * OBW && 31 + 32 * HDRW <= 32 * OBW && 31 + 1
               "a step, a header and a carried piece each fit the flushed bit buffer");
 constexpr uint32_t NONE = 0xFFFFFFFFu;
 
-struct Args {
+// What every kernel of the stream frame (below) is given; deflate_batch_lz.hip's Args start with it too.
+struct FrameArgs {
     const uint8_t* in;
     uint8_t* out;
     const ndfl_member_item* items;
@@ -62,6 +63,9 @@ struct Args {
     uint32_t n;
     uint32_t chunk_len;
     uint32_t* ticket;         // zeroed
+};
+
+struct Args : FrameArgs {
     int32_t hist_enabled;     // historyLookbehindLimit > 0
     int32_t rle;              // 1: RLE preset (dist 1, runs 3..258); 0: LITERAL preset
     int32_t dynamic;
@@ -69,7 +73,8 @@ struct Args {
     const uint32_t* crc_x;    // x^(8k) k<64 then x^(8*64k) k<1024
 };
 
-// LDS of one wave: 12,632 bytes, 12 waves per CU (3 per SIMD; 160 KiB / 12,632 = 12.97).
+// LDS of one wave: 12,632 bytes, 12 waves per CU (3 per SIMD; 160 KiB / 12,632 = 12.97).  The stream
+// frame's part of it: deflate_batch_lz.hip's Lds adds its head table behind.
 struct Lds {
     HuffScr scr;              // (first: pm_lengths reads its keys 16 bytes at a time)
     uint32_t litCode[288];    // rev(code) | len << 16
@@ -267,10 +272,27 @@ __device__ __forceinline__ void load_lane(const uint8_t* p, uint32_t vcnt, uint3
     }
 }
 
-// A step's L bytes (lane `lane` holds the vcnt bytes from step position t0 on, load_lane) into the
-// checksum ck (kind: NDFL_SUM_*).
-__device__ __forceinline__ void fold_step(uint64_t v_tab, uint32_t kind, int lane, uint32_t L, uint32_t t0, uint32_t vcnt,
-                                          uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t& ck) {
+// One step of a walk over a chunk's bytes, 64 lanes x BPL contiguous bytes: the step has L bytes, of
+// which lane `lane` holds the vcnt from step position t0 on (w0..w3, load_lane).
+struct Step {
+    int lane;
+    uint32_t t0, L, vcnt, w0, w1, w2, w3;
+};
+// The step at byte sb of the len_c bytes at cp.
+__device__ __forceinline__ Step load_step(const uint8_t* cp, uint32_t len_c, uint32_t sb) {
+    Step q;
+    q.lane = opaque_lane();
+    q.t0 = (uint32_t)q.lane * BPL;
+    q.L = min(STEP, len_c - sb);
+    q.vcnt = q.L > q.t0 ? min(BPL, q.L - q.t0) : 0u;
+    load_lane(cp + sb + q.t0, q.vcnt, q.w0, q.w1, q.w2, q.w3);
+    return q;
+}
+
+// A step's bytes into the checksum ck (kind: NDFL_SUM_*).
+__device__ __forceinline__ void fold_step(uint64_t v_tab, uint32_t kind, const Step& q, uint32_t& ck) {
+    const int lane = q.lane;
+    const uint32_t L = q.L, t0 = q.t0, vcnt = q.vcnt, w0 = q.w0, w1 = q.w1, w2 = q.w2, w3 = q.w3;
     const uint32_t after = vcnt ? L - (t0 + vcnt) : 0u;      // the step's bytes behind this lane's
     if (kind == NDFL_SUM_CRC32) {
         const uint32_t* T0 = (const uint32_t*)(uintptr_t)to_s(v_tab);     // slicing-by-4 tables, then x^(8k)
@@ -352,6 +374,9 @@ __device__ __forceinline__ uint32_t walk_chunk(bool rle, uint64_t v_tab, Lds& S,
     bool open = false;
     uint32_t cval = 0, clen = 0, clead = 1;
     for (uint32_t sb = 0; sb < len_c; sb += STEP) {
+        // load_step's text, kept here: with the step taken from load_step the compiler orders the start
+        // mask below differently, and the kernel was 1.5 % slower on 512-byte streams (and 3.4 % faster on
+        // 1 MiB ones): profiles/batch_frame_ab.txt
         const int lane = opaque_lane();
         const uint32_t t0 = (uint32_t)lane * BPL;
         const uint32_t L = min(STEP, len_c - sb);
@@ -359,7 +384,7 @@ __device__ __forceinline__ uint32_t walk_chunk(bool rle, uint64_t v_tab, Lds& S,
         uint32_t w0, w1, w2, w3;
         load_lane(cp + sb + t0, vcnt, w0, w1, w2, w3);
         // ---- checksum of the bytes on their way through -------------------------------------------
-        if (EMIT) fold_step(v_tab, kind, lane, L, t0, vcnt, w0, w1, w2, w3, ck);
+        if (EMIT) { Step q{lane, t0, L, vcnt, w0, w1, w2, w3}; fold_step(v_tab, kind, q, ck); }
         // ---- piece starts: bit i = byte i differs from the byte before it ---------------------------
         uint32_t F;
         {
@@ -427,72 +452,169 @@ __device__ __forceinline__ uint32_t walk_chunk(bool rle, uint64_t v_tab, Lds& S,
     return prevb;
 }
 
+// ---- the stream frame ------------------------------------------------------------------------------
+// What ndfl_deflate_batch_kernel and ndfl_deflate_batch_lz_kernel (deflate_batch_lz.hip) do around a
+// block's tokens: claim a stream, start it, start and end a dynamic block's histograms, put the header
+// and the end-of-block code, finish the stream.  One text for both, forced inline.
+//
+// The frame's arguments are needed once per stream or per chunk: parked (see to_v).
+struct Frame {
+    uint64_t v_in, v_out, v_items, v_results, v_ticket;
+    uint32_t v_n, v_chunk_len;
+};
+__device__ __forceinline__ Frame park_frame(const FrameArgs& a) {
+    Frame f;
+    f.v_in = to_v((uint64_t)(uintptr_t)a.in); f.v_out = to_v((uint64_t)(uintptr_t)a.out);
+    f.v_items = to_v((uint64_t)(uintptr_t)a.items); f.v_results = to_v((uint64_t)(uintptr_t)a.results);
+    f.v_ticket = to_v((uint64_t)(uintptr_t)a.ticket);
+    f.v_n = to_v(a.n); f.v_chunk_len = to_v(a.chunk_len);
+    return f;
+}
+
+// The stream's constants, parked too, and its running checksum, parked across the code construction.
+struct Stream {
+    uint32_t v_si;            // its index
+    uint64_t v_src, v_len;    // in + in_off, in_len
+    uint32_t v_fmt, v_kind;   // NDFL_FMT_*; NDFL_SUM_*: the container's, else the item's
+    uint32_t v_ck;
+};
+
+// The next stream index from the ticket; false when none is left.
+__device__ __forceinline__ bool claim_stream(Lds& S, const Frame& f, Stream& st) {
+    __syncthreads();
+    if (opaque_lane() == 0) S.ticket = atomicAdd((uint32_t*)(uintptr_t)to_s(f.v_ticket), 1u);
+    __syncthreads();
+    st.v_si = to_v(S.ticket);
+    return to_s(st.v_si) < to_s(f.v_n);
+}
+
+// The claimed stream's item into st, its checksum's initial value, and its output: an empty, zeroed
+// bit buffer at the region's first byte.
+__device__ __forceinline__ BitOut begin_stream(Lds& S, const Frame& f, Stream& st) {
+    BitOut bo{S.obuf, 0ull, 0ull, to_v((uint64_t)0), 0u};
+    {
+        const ndfl_member_item it = ((const ndfl_member_item*)(uintptr_t)to_s(f.v_items))[to_s(st.v_si)];
+        st.v_src = to_v(to_s(f.v_in) + it.in_off); st.v_len = to_v(it.in_len);
+        bo.v_optr = to_v(to_s(f.v_out) + it.out_off); bo.v_cap = to_v(it.out_cap);
+        st.v_fmt = to_v(it.format);
+        st.v_kind = to_v(it.format == NDFL_FMT_ZLIB ? NDFL_SUM_ADLER32 : it.format == NDFL_FMT_GZIP ? NDFL_SUM_CRC32 : it.sum);
+    }
+    {
+        const uint32_t kind = to_s(st.v_kind);
+        st.v_ck = to_v(kind == NDFL_SUM_CRC32 ? 0xFFFFFFFFu : kind == NDFL_SUM_ADLER32 ? 1u : 0u);
+    }
+    for (uint32_t j = (uint32_t)opaque_lane(); j <= OBW; j += 64) S.obuf[j] = 0;
+    return bo;
+}
+
+// A dynamic block's histograms: zeroed before its tokens are counted (the caller syncs) ...
+__device__ __forceinline__ void begin_block_hist(Lds& S) {
+    const int lane = opaque_lane();
+    for (int t = lane; t < 288; t += 64) S.scr.hlit[t] = 0;
+    if (lane < 32) S.scr.hdist[lane] = 0;
+}
+// ... and, after them, the counts that no byte of the chunk gives.
+__device__ __forceinline__ void end_block_hist(Lds& S, uint32_t len_c) {
+    if (opaque_lane() == 0) {
+        atomicAdd(&S.scr.hlit[256], 1u);                  // end of block (D/comp/Lz77Huffman.java:131-132)
+        if (len_c == 0) atomicAdd(&S.scr.hlit[0], 1u);    // (:146-147)
+    }
+}
+
+// The block's header (S.scr.hdr(), hb bits, zero past them) into the bit buffer.
+__device__ __forceinline__ void put_header(Lds& S, BitOut& bo, uint32_t hb) {
+    make_room(bo, hb);
+    for (uint32_t k = (uint32_t)opaque_lane(); 32 * k < hb; k += 64) {
+        const uint32_t nbk = min(32u, hb - 32 * k), word = S.scr.hdr()[k];
+        BitPut bp; bp.init(bo.obuf, bo.fill + 32 * k);
+        bp.put(word & 0xFFFF, min(nbk, 16u));
+        if (nbk > 16) bp.put(word >> 16, nbk - 16);
+        bp.flush();
+    }
+    bo.fill += hb;
+}
+
+// The end-of-block code (D/comp/Lz77Huffman.java:285).
+__device__ __forceinline__ void put_eob(Lds& S, BitOut& bo) {
+    const uint32_t eob = rfl(S.litCode[256]);
+    make_room(bo, eob >> 16);
+    if (opaque_lane() == 0) put_end_of_block(bo.obuf, bo.fill, eob);
+    bo.fill += eob >> 16;
+}
+
+// finish(): pad to a byte (zero bits), then the container's trailer, the bit buffer's last bytes and
+// the stream's result.  v_fill: the bit buffer's fill after the last block.
+__device__ __forceinline__ void finish_stream(const Frame& f, const Stream& st, BitOut& bo, uint32_t v_fill) {
+    bo.fill = to_s(v_fill);
+    const uint64_t v_end_bits = to_v(to_s(bo.v_wbase) * 8 + bo.fill);
+    const uint32_t fmt = to_s(st.v_fmt);
+    const uint32_t sum = to_s(st.v_kind) == NDFL_SUM_CRC32 ? ~to_s(st.v_ck) : to_s(st.v_ck);
+    const uint32_t tl = fmt == NDFL_FMT_ZLIB ? 4u : fmt == NDFL_FMT_GZIP ? 8u : 0u;
+    make_room(bo, 7 + 64);
+    bo.fill = (bo.fill + 7) & ~7u;
+    const int lane = opaque_lane();
+    if (lane == 0 && tl) {
+        BitPut bp; bp.init(bo.obuf, bo.fill);
+        if (fmt == NDFL_FMT_ZLIB) {                               // big-endian Adler-32
+            for (int k = 3; k >= 0; k--) bp.put((sum >> (8 * k)) & 0xFFu, 8);
+        } else {                                                  // CRC-32, ISIZE: little-endian
+            const uint32_t isz = (uint32_t)st.v_len;
+            for (int k = 0; k < 4; k++) bp.put((sum >> (8 * k)) & 0xFFu, 8);
+            for (int k = 0; k < 4; k++) bp.put((isz >> (8 * k)) & 0xFFu, 8);
+        }
+        bp.flush();
+    }
+    bo.fill += 8 * tl;
+    __syncthreads();
+    store_bytes(bo, bo.fill >> 3);
+    if (lane == 0) {
+        ndfl_deflate_result rr;
+        rr.out_len = bo.v_wbase + (bo.fill >> 3);
+        rr.status = rr.out_len > bo.v_cap ? NDFL_E_CAPACITY : 0;
+        rr.checksum = sum;
+        rr.end_bits = v_end_bits;
+        ((ndfl_deflate_result*)(uintptr_t)f.v_results)[st.v_si] = rr;
+    }
+}
+
 }  // namespace dbat
 
 extern "C" __global__ void __launch_bounds__(64)
 ndfl_deflate_batch_kernel(dbat::Args a) {
     using namespace dbat;
     __shared__ __attribute__((aligned(16))) Lds S;
-    // the arguments are needed once per stream or per chunk: parked (see to_v)
-    const uint64_t v_in = to_v((uint64_t)(uintptr_t)a.in), v_out = to_v((uint64_t)(uintptr_t)a.out);
-    const uint64_t v_items = to_v((uint64_t)(uintptr_t)a.items), v_results = to_v((uint64_t)(uintptr_t)a.results);
-    const uint64_t v_ticket = to_v((uint64_t)(uintptr_t)a.ticket), v_tab = to_v((uint64_t)(uintptr_t)a.crc_tab);
-    const uint32_t v_n = to_v(a.n), v_chunk_len = to_v(a.chunk_len);
+    const Frame f = park_frame(a);
+    const uint64_t v_tab = to_v((uint64_t)(uintptr_t)a.crc_tab);
     const uint32_t v_rle = to_v((uint32_t)(a.rle != 0)), v_dyn = to_v((uint32_t)(a.dynamic != 0));
     const uint32_t v_hist = to_v((uint32_t)(a.hist_enabled != 0));
     for (;;) {
-        __syncthreads();
-        if (opaque_lane() == 0) S.ticket = atomicAdd((uint32_t*)(uintptr_t)to_s(v_ticket), 1u);
-        __syncthreads();
-        const uint32_t v_si = to_v(S.ticket);
-        if (to_s(v_si) >= to_s(v_n)) break;
-        // the stream's constants, parked too
-        uint64_t v_src, v_len;
-        uint32_t v_fmt, v_kind;
-        BitOut bo{S.obuf, 0ull, 0ull, to_v((uint64_t)0), 0u};
-        {
-            const ndfl_member_item it = ((const ndfl_member_item*)(uintptr_t)to_s(v_items))[to_s(v_si)];
-            v_src = to_v(to_s(v_in) + it.in_off); v_len = to_v(it.in_len);
-            bo.v_optr = to_v(to_s(v_out) + it.out_off); bo.v_cap = to_v(it.out_cap);
-            v_fmt = to_v(it.format);
-            v_kind = to_v(it.format == NDFL_FMT_ZLIB ? NDFL_SUM_ADLER32 : it.format == NDFL_FMT_GZIP ? NDFL_SUM_CRC32 : it.sum);
-        }
+        Stream st;
+        if (!claim_stream(S, f, st)) break;
+        BitOut bo = begin_stream(S, f, st);
         // the running state: parked across the code construction
-        uint32_t v_ck, v_prevb = to_v(0u), v_fill = to_v(0u);
+        uint32_t v_prevb = to_v(0u), v_fill = to_v(0u);
         uint64_t v_cs = to_v((uint64_t)0);
-        {
-            const uint32_t kind = to_s(v_kind);
-            v_ck = to_v(kind == NDFL_SUM_CRC32 ? 0xFFFFFFFFu : kind == NDFL_SUM_ADLER32 ? 1u : 0u);
-        }
-        for (uint32_t j = (uint32_t)opaque_lane(); j <= OBW; j += 64) S.obuf[j] = 0;
         for (;;) {
             Codes cd{S.litCode, 0u, 0u, 0u, 0u};
             if (to_s(v_dyn)) {
-                {
-                    const int lane = opaque_lane();
-                    for (int t = lane; t < 288; t += 64) S.scr.hlit[t] = 0;
-                    if (lane < 32) S.scr.hdist[lane] = 0;
-                }
+                begin_block_hist(S);
                 __syncthreads();
                 const uint64_t cs = to_s(v_cs);
-                const uint32_t len_c = (uint32_t)min((uint64_t)to_s(v_chunk_len), to_s(v_len) - cs);
+                const uint32_t len_c = (uint32_t)min((uint64_t)to_s(f.v_chunk_len), to_s(st.v_len) - cs);
                 {
                     // chunk 0 has no history; a later chunk has the stream's previous byte when hist_limit > 0
                     const bool zl = to_s(v_rle) && cs > 0 && to_s(v_hist);
                     uint32_t nock = 0;
-                    walk_chunk<false>(to_s(v_rle) != 0, v_tab, S, bo, cd, (const uint8_t*)(uintptr_t)(to_s(v_src) + cs), len_c,
-                                      to_s(v_prevb), zl, NDFL_SUM_NONE, nock);
+                    walk_chunk<false>(to_s(v_rle) != 0, v_tab, S, bo, cd, (const uint8_t*)(uintptr_t)(to_s(st.v_src) + cs),
+                                      len_c, to_s(v_prevb), zl, NDFL_SUM_NONE, nock);
                 }
-                if (opaque_lane() == 0) {
-                    atomicAdd(&S.scr.hlit[256], 1u);                  // end of block (:131-132)
-                    if (len_c == 0) atomicAdd(&S.scr.hlit[0], 1u);    // (:146-147)
-                }
+                end_block_hist(S, len_c);
             }
             __syncthreads();
             uint32_t hb;
             {
-                const uint64_t len = to_s(v_len), cs = to_s(v_cs);
-                const bool is_final = len - cs <= (uint64_t)to_s(v_chunk_len);
+                const uint64_t len = to_s(st.v_len), cs = to_s(v_cs);
+                const bool is_final = len - cs <= (uint64_t)to_s(f.v_chunk_len);
                 hb = build_block_codes<64, true>(S.scr, to_s(v_dyn) != 0, is_final, S.litCode, S.distCode);
             }
             {
@@ -502,152 +624,72 @@ ndfl_deflate_batch_kernel(dbat::Args a) {
                 cd.m258l = (c285 >> 16) + cd.d0l;
             }
             bo.fill = to_s(v_fill);
-            // the header (S.scr.hdr(), zero past its bits) into the bit buffer
-            make_room(bo, hb);
-            for (uint32_t k = (uint32_t)opaque_lane(); 32 * k < hb; k += 64) {
-                const uint32_t nbk = min(32u, hb - 32 * k), word = S.scr.hdr()[k];
-                BitPut bp; bp.init(bo.obuf, bo.fill + 32 * k);
-                bp.put(word & 0xFFFF, min(nbk, 16u));
-                if (nbk > 16) bp.put(word >> 16, nbk - 16);
-                bp.flush();
-            }
-            bo.fill += hb;
+            put_header(S, bo, hb);
             {
                 const uint64_t cs = to_s(v_cs);
-                const uint32_t len_c = (uint32_t)min((uint64_t)to_s(v_chunk_len), to_s(v_len) - cs);
+                const uint32_t len_c = (uint32_t)min((uint64_t)to_s(f.v_chunk_len), to_s(st.v_len) - cs);
                 const bool zl = to_s(v_rle) && cs > 0 && to_s(v_hist);
-                uint32_t ck = to_s(v_ck);
+                uint32_t ck = to_s(st.v_ck);
                 v_prevb = to_v(walk_chunk<true>(to_s(v_rle) != 0, v_tab, S, bo, cd,
-                                                (const uint8_t*)(uintptr_t)(to_s(v_src) + cs), len_c, to_s(v_prevb), zl,
-                                                to_s(v_kind), ck));
-                v_ck = to_v(ck);
+                                                (const uint8_t*)(uintptr_t)(to_s(st.v_src) + cs), len_c, to_s(v_prevb), zl,
+                                                to_s(st.v_kind), ck));
+                st.v_ck = to_v(ck);
                 v_cs = to_v(cs + len_c);
             }
-            // the end-of-block code (D/comp/Lz77Huffman.java:285)
-            const uint32_t eob = rfl(S.litCode[256]);
-            make_room(bo, eob >> 16);
-            if (opaque_lane() == 0) put_end_of_block(bo.obuf, bo.fill, eob);
-            bo.fill += eob >> 16;
+            put_eob(S, bo);
             v_fill = to_v(bo.fill);
-            if (to_s(v_cs) >= to_s(v_len)) break;
+            if (to_s(v_cs) >= to_s(st.v_len)) break;
         }
-        // finish(): pad to a byte (zero bits), then the container's trailer
-        bo.fill = to_s(v_fill);
-        const uint64_t v_end_bits = to_v(to_s(bo.v_wbase) * 8 + bo.fill);
-        const uint32_t fmt = to_s(v_fmt);
-        const uint32_t sum = to_s(v_kind) == NDFL_SUM_CRC32 ? ~to_s(v_ck) : to_s(v_ck);
-        const uint32_t tl = fmt == NDFL_FMT_ZLIB ? 4u : fmt == NDFL_FMT_GZIP ? 8u : 0u;
-        make_room(bo, 7 + 64);
-        bo.fill = (bo.fill + 7) & ~7u;
-        const int lane = opaque_lane();
-        if (lane == 0 && tl) {
-            BitPut bp; bp.init(bo.obuf, bo.fill);
-            if (fmt == NDFL_FMT_ZLIB) {                               // big-endian Adler-32
-                for (int k = 3; k >= 0; k--) bp.put((sum >> (8 * k)) & 0xFFu, 8);
-            } else {                                                  // CRC-32, ISIZE: little-endian
-                const uint32_t isz = (uint32_t)v_len;
-                for (int k = 0; k < 4; k++) bp.put((sum >> (8 * k)) & 0xFFu, 8);
-                for (int k = 0; k < 4; k++) bp.put((isz >> (8 * k)) & 0xFFu, 8);
-            }
-            bp.flush();
-        }
-        bo.fill += 8 * tl;
-        __syncthreads();
-        store_bytes(bo, bo.fill >> 3);
-        if (lane == 0) {
-            ndfl_deflate_result rr;
-            rr.out_len = bo.v_wbase + (bo.fill >> 3);
-            rr.status = rr.out_len > bo.v_cap ? NDFL_E_CAPACITY : 0;
-            rr.checksum = sum;
-            rr.end_bits = v_end_bits;
-            ((ndfl_deflate_result*)(uintptr_t)v_results)[v_si] = rr;
-        }
+        finish_stream(f, st, bo, v_fill);
     }
 }
 
 // ---- host side ------------------------------------------------------------------------------------
-// The launch of ndfl_deflate_batch_kernel for deflate_batch_run: the grid, then the kernel between the
-// two events.
+// batch_run's launcher for ndfl_deflate_batch_kernel.
 struct BatchRleLaunch {
     const Knobs& knobs;
-    uint32_t n;
-    int rle, dyn;
-    uint32_t chunk_len, hist_limit;
-    const uint32_t* crc_tabs;
-    int operator()(hipStream_t s, const uint8_t* d_src, uint8_t* d_out, const ndfl_member_item* d_items,
-                   ndfl_deflate_result* d_res, uint32_t* d_ticket, hipEvent_t e0, hipEvent_t e1) {
-        static const uint32_t auto_grid = wave_grid(ndfl_deflate_batch_kernel, 256 * 16);
-        uint32_t grid = std::min(n, auto_grid);
-        if (knobs.batch_waves) grid = std::min(grid, knobs.batch_waves);
-        if (knobs.stats) fprintf(stderr, "[ndfl] deflate batch: %u streams, %u waves (of %u)\n", n, grid, auto_grid);
-        dbat::Args a;
-        a.in = d_src; a.out = d_out; a.items = d_items; a.results = d_res; a.n = n;
-        a.chunk_len = chunk_len; a.ticket = d_ticket; a.hist_enabled = hist_limit > 0; a.rle = rle; a.dynamic = dyn;
-        a.crc_tab = crc_tabs; a.crc_x = crc_tabs + 1024;
-        INF_CHK(hipEventRecord(e0, s));
+    dbat::Args a;                         // n, chunk_len, the preset and the tables; deflate_batch_run sets `in`
+    uint32_t grid = 0;
+    int prepare() {                       // (before the launch is timed)
+        grid = batch_grid<ndfl_deflate_batch_kernel>(a.n, knobs, "deflate batch");
+        return 0;
+    }
+    int operator()(hipStream_t s, uint8_t* d_out, const ndfl_member_item* d_items, ndfl_deflate_result* d_res,
+                   uint32_t* d_ticket) {
+        a.out = d_out; a.items = d_items; a.results = d_res; a.ticket = d_ticket;
         hipLaunchKernelGGL(ndfl_deflate_batch_kernel, dim3(grid), dim3(64), 0, s, a);
-        INF_CHK(hipGetLastError());
-        INF_CHK(hipEventRecord(e1, s));
         return 0;
     }
 };
 
-// The batch on stream s (arguments already validated): one launch (`launch`: BatchRleLaunch, or
-// deflate_batch_lz.hip's BatchLzLaunch), one host sync.  Host input is staged in B.d_in (the span of
-// `in` the items cover), host output in B.d_out as inflate_batch_run does, and only each stream's
-// stored bytes are copied into `out`.
+// Host input of a deflate batch: the span of `in` the items cover, staged in *d_in.  *d_src = the
+// kernel's `in` (item offsets are relative to it).
+static int stage_span(void** d_in, size_t* d_in_cap, hipStream_t s, const uint8_t* in, const ndfl_member_item* items,
+                      uint32_t n, uint32_t flags, const uint8_t** d_src) {
+    *d_src = in;
+    if (flags & 1u) return 0;
+    uint64_t lo = ~0ull, hi = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        if (!items[i].in_len) continue;
+        lo = std::min(lo, items[i].in_off);
+        hi = std::max(hi, items[i].in_off + items[i].in_len);
+    }
+    if (hi > lo) {
+        INF_CHK(inf_ensure(d_in, d_in_cap, hi - lo));
+        INF_CHK(hipMemcpyAsync(*d_in, in + lo, hi - lo, hipMemcpyHostToDevice, s));
+    }
+    *d_src = (const uint8_t*)*d_in - (hi > lo ? lo : 0);
+    return 0;
+}
+
+// ndfl_deflate_batch and ndfl_deflate_batch_lz77 on stream s (arguments already validated).  `launch`: a
+// BatchRleLaunch, or deflate_batch_lz.hip's BatchLzLaunch.
 template <class Launch>
 static int deflate_batch_run(BatchScratch& B, void** d_in, size_t* d_in_cap, hipStream_t s, hipEvent_t e0, hipEvent_t e1,
                              const uint8_t* in, uint8_t* out, const ndfl_member_item* items,
                              ndfl_deflate_result* results, uint32_t n, uint32_t flags, Launch launch, double* last_ms) {
-    uint64_t ilo = ~0ull, ihi = 0, lo = ~0ull, hi = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        if (items[i].in_len) {
-            ilo = std::min(ilo, items[i].in_off);
-            ihi = std::max(ihi, items[i].in_off + items[i].in_len);
-        }
-        if (items[i].out_cap) {
-            lo = std::min(lo, items[i].out_off);
-            hi = std::max(hi, items[i].out_off + items[i].out_cap);
-        }
-    }
-    const uint8_t* d_src = in;                   // the kernel's `in` (item offsets are relative to it)
-    if (!(flags & 1u)) {
-        if (ihi > ilo) {
-            INF_CHK(inf_ensure(d_in, d_in_cap, ihi - ilo));
-            INF_CHK(hipMemcpyAsync(*d_in, in + ilo, ihi - ilo, hipMemcpyHostToDevice, s));
-        }
-        d_src = (const uint8_t*)*d_in - (ihi > ilo ? ilo : 0);
-    }
-    const size_t items_b = (size_t)n * sizeof(ndfl_member_item), res_b = (size_t)n * sizeof(ndfl_deflate_result);
-    INF_CHK(inf_ensure(&B.d_items, &B.d_items_cap, items_b + res_b + 16));
-    ndfl_deflate_result* d_res = (ndfl_deflate_result*)((char*)B.d_items + items_b);
-    uint32_t* d_ticket = (uint32_t*)((char*)d_res + res_b);
-    INF_CHK(hipMemcpyAsync(B.d_items, items, items_b, hipMemcpyHostToDevice, s));
-    INF_CHK(hipMemsetAsync(d_ticket, 0, 16, s));
-    const bool out_dev = (flags & 2u) != 0;
-    uint8_t* d_out = out;
-    std::vector<uint8_t> h_span;
-    if (!out_dev) {
-        if (hi > lo) INF_CHK(inf_ensure(&B.d_out, &B.d_out_cap, hi - lo));
-        d_out = (uint8_t*)B.d_out - (hi > lo ? lo : 0);
-    }
-    {
-        const int r = launch(s, d_src, d_out, (const ndfl_member_item*)B.d_items, d_res, d_ticket, e0, e1);
-        if (r) return r;
-    }
-    INF_CHK(hipMemcpyAsync(results, d_res, res_b, hipMemcpyDeviceToHost, s));
-    if (!out_dev && hi > lo) {
-        h_span.resize(hi - lo);
-        INF_CHK(hipMemcpyAsync(h_span.data(), B.d_out, hi - lo, hipMemcpyDeviceToHost, s));
-    }
-    INF_CHK(hipStreamSynchronize(s));
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) *last_ms = ms;
-    if (!out_dev)
-        for (uint32_t i = 0; i < n; i++) {
-            const uint64_t nb = std::min(results[i].out_len, items[i].out_cap);
-            if (nb) memcpy(out + items[i].out_off, h_span.data() + (items[i].out_off - lo), nb);
-        }
-    return 0;
+    INF_RC(stage_span(d_in, d_in_cap, s, in, items, n, flags, &launch.a.in));
+    INF_RC(launch.prepare());
+    return batch_run(B, s, e0, e1, out, items, results, n, flags, last_ms, launch);
 }
+

@@ -1,9 +1,10 @@
 // deflate_batch_lz.hip -- batched LZ77 deflate: many independent buffers compressed in one launch with
 // any Lz77Huffman(dynamic, minRun, maxRun, minDist, maxDist), FULL_* among them
 // (ndfl_deflate_batch_lz77, include/ndfl.h).  The LZ77 counterpart of deflate_batch.hip, whose launch
-// shape, bit buffer, region stores, checksum folding and trailers it shares (dbat::): a persistent grid
-// of one-wave workgroups, an atomic ticket over the stream indices, each stream encoded chunk by chunk,
-// serially, by one wave that waits on no other.
+// shape, bit buffer, region stores, checksum folding and stream frame (the ticket claim, the stream's
+// start, the header, the end-of-block code, the trailer and the result) it shares (dbat::): a persistent
+// grid of one-wave workgroups, an atomic ticket over the stream indices, each stream encoded chunk by
+// chunk, serially, by one wave that waits on no other.
 //
 // ndfl_deflate_chunks_lz77 searches with three kernels over one staging buffer with one history start
 // (LzArgs.vstart).  Here a wave carries its stream's history itself: the hash chains of the stream run
@@ -42,7 +43,6 @@ using dbat::BitOut;
 using dbat::make_room;
 using dbat::OBW;
 using dbat::rfl;
-using dbat::store_bytes;
 using dbat::to_s;
 using dbat::to_v;
 
@@ -60,14 +60,7 @@ static_assert(31 + 64 * 48 <= 32 * OBW, "a step of 64 tokens fits the flushed bi
 
 __device__ __forceinline__ uint32_t hash3(uint32_t k) { return (k * 2654435761u) >> (32 - HBITS); }
 
-struct Args {
-    const uint8_t* in;
-    uint8_t* out;
-    const ndfl_member_item* items;
-    ndfl_deflate_result* results;
-    uint32_t n;
-    uint32_t chunk_len;
-    uint32_t* ticket;         // zeroed
+struct Args : dbat::FrameArgs {
     uint32_t hist_limit;
     int32_t dynamic;
     uint32_t min_run, max_run, min_dist, max_dist;    // 3 <= min_run <= max_run <= 258, 1 <= min_dist <= max_dist <= 32768
@@ -79,13 +72,8 @@ struct Args {
 };
 
 // LDS of one wave: 20,824 bytes, 7 waves per CU (160 KiB / 20,824 = 7.87).
-struct Lds {
-    HuffScr scr;              // (first: pm_lengths reads its keys 16 bytes at a time)
-    uint32_t litCode[288];    // rev(code) | len << 16
-    uint32_t distCode[32];
-    uint32_t obuf[OBW + 1];   // bit buffer (dbat::BitOut)
+struct Lds : dbat::Lds {      // (HuffScr first, the codes, the bit buffer, the ticket)
     uint16_t head[NHEAD];     // bucket -> offset of its last position from the base, or HNONE
-    uint32_t ticket;
 };
 
 struct Search {
@@ -105,21 +93,11 @@ __device__ __forceinline__ uint32_t ld4(const uint8_t* P, uint32_t r, uint32_t r
     return w;
 }
 
-// The chunk's bytes into the checksum ck (kind: NDFL_SUM_*), 64 lanes x 16 bytes a step: the load and the
-// folding of dbat::walk_chunk<true>.
+// The chunk's bytes into the checksum ck (kind: NDFL_SUM_*): the steps and the folding of
+// dbat::walk_chunk<true>.
 __device__ __forceinline__ void fold_chunk(uint64_t v_tab, const uint8_t* cp, uint32_t len_c, uint32_t kind, uint32_t& ck) {
-    using dbat::BPL;
-    using dbat::STEP;
     if (kind == NDFL_SUM_NONE) return;
-    for (uint32_t sb = 0; sb < len_c; sb += STEP) {
-        const int lane = opaque_lane();
-        const uint32_t t0 = (uint32_t)lane * BPL;
-        const uint32_t L = min(STEP, len_c - sb);
-        const uint32_t vcnt = L > t0 ? min(BPL, L - t0) : 0u;
-        uint32_t w0, w1, w2, w3;
-        dbat::load_lane(cp + sb + t0, vcnt, w0, w1, w2, w3);
-        dbat::fold_step(v_tab, kind, lane, L, t0, vcnt, w0, w1, w2, w3, ck);
-    }
+    for (uint32_t sb = 0; sb < len_c; sb += dbat::STEP) dbat::fold_step(v_tab, kind, dbat::load_step(cp, len_c, sb), ck);
 }
 
 // Link, search and parse of one chunk.  Positions are window-relative: P = the stream's byte at offset
@@ -287,132 +265,63 @@ ndfl_deflate_batch_lz_kernel(dblz::Args a) {
     using namespace dblz;
     __shared__ __attribute__((aligned(16))) Lds S;
     // the arguments are needed once per stream or per chunk: parked (dbat::to_v)
-    const uint64_t v_in = to_v((uint64_t)(uintptr_t)a.in), v_out = to_v((uint64_t)(uintptr_t)a.out);
-    const uint64_t v_items = to_v((uint64_t)(uintptr_t)a.items), v_results = to_v((uint64_t)(uintptr_t)a.results);
-    const uint64_t v_ticket = to_v((uint64_t)(uintptr_t)a.ticket), v_tab = to_v((uint64_t)(uintptr_t)a.crc_tab);
+    const dbat::Frame f = dbat::park_frame(a);
+    const uint64_t v_tab = to_v((uint64_t)(uintptr_t)a.crc_tab);
     const uint64_t v_ring = to_v((uint64_t)(uintptr_t)(a.ring + (size_t)blockIdx.x * ((size_t)a.ring_mask + 1)));
     const uint64_t v_toks = to_v((uint64_t)(uintptr_t)(a.toks + (size_t)blockIdx.x * a.tok_cap));
     const uint32_t v_mask = to_v(a.ring_mask);
-    const uint32_t v_n = to_v(a.n), v_chunk_len = to_v(a.chunk_len), v_hist = to_v(a.hist_limit);
+    const uint32_t v_hist = to_v(a.hist_limit);
     const uint32_t v_dyn = to_v((uint32_t)(a.dynamic != 0));
     const uint32_t v_minr = to_v(a.min_run), v_maxr = to_v(a.max_run), v_mind = to_v(a.min_dist), v_maxd = to_v(a.max_dist);
     for (;;) {
-        __syncthreads();
-        if (opaque_lane() == 0) S.ticket = atomicAdd((uint32_t*)(uintptr_t)to_s(v_ticket), 1u);
-        __syncthreads();
-        const uint32_t v_si = to_v(S.ticket);
-        if (to_s(v_si) >= to_s(v_n)) break;
-        // the stream's constants, parked too
-        uint64_t v_src, v_len;
-        uint32_t v_fmt, v_kind;
-        BitOut bo{S.obuf, 0ull, 0ull, to_v((uint64_t)0), 0u};
-        {
-            const ndfl_member_item it = ((const ndfl_member_item*)(uintptr_t)to_s(v_items))[to_s(v_si)];
-            v_src = to_v(to_s(v_in) + it.in_off); v_len = to_v(it.in_len);
-            bo.v_optr = to_v(to_s(v_out) + it.out_off); bo.v_cap = to_v(it.out_cap);
-            v_fmt = to_v(it.format);
-            v_kind = to_v(it.format == NDFL_FMT_ZLIB ? NDFL_SUM_ADLER32 : it.format == NDFL_FMT_GZIP ? NDFL_SUM_CRC32 : it.sum);
-        }
-        // the running state, all of it started afresh for the stream: checksum, bit buffer, head table and
-        // its base (the ring needs no clearing: lz_chunk reads only links this stream has written)
-        uint32_t v_ck, v_fill = to_v(0u), v_cb = to_v(0u);
+        dbat::Stream st;
+        if (!dbat::claim_stream(S, f, st)) break;
+        // the running state, all of it started afresh for the stream: checksum and bit buffer (begin_stream),
+        // head table and its base (the ring needs no clearing: lz_chunk reads only links this stream has written)
+        BitOut bo = dbat::begin_stream(S, f, st);
+        uint32_t v_fill = to_v(0u), v_cb = to_v(0u);
         uint64_t v_cs = to_v((uint64_t)0);
-        {
-            const uint32_t kind = to_s(v_kind);
-            v_ck = to_v(kind == NDFL_SUM_CRC32 ? 0xFFFFFFFFu : kind == NDFL_SUM_ADLER32 ? 1u : 0u);
-        }
-        for (uint32_t j = (uint32_t)opaque_lane(); j <= OBW; j += 64) S.obuf[j] = 0;
         for (uint32_t j = (uint32_t)opaque_lane(); j < NHEAD / 2; j += 64) ((uint32_t*)S.head)[j] = HNONE << 16 | HNONE;
         for (;;) {
-            if (to_s(v_dyn)) {
-                const int lane = opaque_lane();
-                for (int t = lane; t < 288; t += 64) S.scr.hlit[t] = 0;
-                if (lane < 32) S.scr.hdist[lane] = 0;
-            }
+            if (to_s(v_dyn)) dbat::begin_block_hist(S);
             __syncthreads();
             uint32_t v_ntok;
             {
-                const uint64_t cs = to_s(v_cs), len = to_s(v_len);
-                const uint32_t len_c = (uint32_t)min((uint64_t)to_s(v_chunk_len), len - cs);
+                const uint64_t cs = to_s(v_cs), len = to_s(st.v_len);
+                const uint32_t len_c = (uint32_t)min((uint64_t)to_s(f.v_chunk_len), len - cs);
                 const uint64_t hs = cs - min((uint64_t)to_s(v_hist), cs);      // chunk 0 has no history
-                const uint8_t* P = (const uint8_t*)(uintptr_t)(to_s(v_src) + hs);
+                const uint8_t* P = (const uint8_t*)(uintptr_t)(to_s(st.v_src) + hs);
                 const uint32_t rc0 = (uint32_t)(cs - hs);
                 const uint32_t rend = (uint32_t)min(len - hs, (uint64_t)rc0 + len_c + 8);
-                uint32_t ck = to_s(v_ck);
-                fold_chunk(v_tab, P + rc0, len_c, to_s(v_kind), ck);
-                v_ck = to_v(ck);
+                uint32_t ck = to_s(st.v_ck);
+                fold_chunk(v_tab, P + rc0, len_c, to_s(st.v_kind), ck);
+                st.v_ck = to_v(ck);
                 const Search sp{to_s(v_minr), to_s(v_maxr), to_s(v_mind), to_s(v_maxd)};
                 uint32_t cb = to_s(v_cb);
                 v_ntok = to_v(lz_chunk(S, sp, P, rc0, len_c, rend, (uint32_t)hs, (uint16_t*)(uintptr_t)to_s(v_ring),
                                        to_s(v_mask), (uint32_t*)(uintptr_t)to_s(v_toks), to_s(v_dyn) != 0, cb));
                 v_cb = to_v(cb + len_c);
-                if (to_s(v_dyn) && opaque_lane() == 0) {
-                    atomicAdd(&S.scr.hlit[256], 1u);                  // end of block (:131-132)
-                    if (len_c == 0) atomicAdd(&S.scr.hlit[0], 1u);    // (:146-147)
-                }
+                if (to_s(v_dyn)) dbat::end_block_hist(S, len_c);
             }
             __syncthreads();                                          // the histograms and the token list
             uint32_t hb;
             {
-                const uint64_t len = to_s(v_len), cs = to_s(v_cs);
-                const bool is_final = len - cs <= (uint64_t)to_s(v_chunk_len);
+                const uint64_t len = to_s(st.v_len), cs = to_s(v_cs);
+                const bool is_final = len - cs <= (uint64_t)to_s(f.v_chunk_len);
                 hb = build_block_codes<64, true>(S.scr, to_s(v_dyn) != 0, is_final, S.litCode, S.distCode);
             }
             bo.fill = to_s(v_fill);
-            // the header (S.scr.hdr(), zero past its bits) into the bit buffer
-            make_room(bo, hb);
-            for (uint32_t k = (uint32_t)opaque_lane(); 32 * k < hb; k += 64) {
-                const uint32_t nbk = min(32u, hb - 32 * k), word = S.scr.hdr()[k];
-                BitPut bp; bp.init(bo.obuf, bo.fill + 32 * k);
-                bp.put(word & 0xFFFF, min(nbk, 16u));
-                if (nbk > 16) bp.put(word >> 16, nbk - 16);
-                bp.flush();
-            }
-            bo.fill += hb;
+            dbat::put_header(S, bo, hb);
             emit_tokens(S, bo, (const uint32_t*)(uintptr_t)to_s(v_toks), to_s(v_ntok));
             {
                 const uint64_t cs = to_s(v_cs);
-                v_cs = to_v(cs + min((uint64_t)to_s(v_chunk_len), to_s(v_len) - cs));
+                v_cs = to_v(cs + min((uint64_t)to_s(f.v_chunk_len), to_s(st.v_len) - cs));
             }
-            // the end-of-block code (D/comp/Lz77Huffman.java:285)
-            const uint32_t eob = rfl(S.litCode[256]);
-            make_room(bo, eob >> 16);
-            if (opaque_lane() == 0) put_end_of_block(bo.obuf, bo.fill, eob);
-            bo.fill += eob >> 16;
+            dbat::put_eob(S, bo);
             v_fill = to_v(bo.fill);
-            if (to_s(v_cs) >= to_s(v_len)) break;
+            if (to_s(v_cs) >= to_s(st.v_len)) break;
         }
-        // finish(): pad to a byte (zero bits), then the container's trailer (as ndfl_deflate_batch_kernel)
-        bo.fill = to_s(v_fill);
-        const uint64_t v_end_bits = to_v(to_s(bo.v_wbase) * 8 + bo.fill);
-        const uint32_t fmt = to_s(v_fmt);
-        const uint32_t sum = to_s(v_kind) == NDFL_SUM_CRC32 ? ~to_s(v_ck) : to_s(v_ck);
-        const uint32_t tl = fmt == NDFL_FMT_ZLIB ? 4u : fmt == NDFL_FMT_GZIP ? 8u : 0u;
-        make_room(bo, 7 + 64);
-        bo.fill = (bo.fill + 7) & ~7u;
-        const int lane = opaque_lane();
-        if (lane == 0 && tl) {
-            BitPut bp; bp.init(bo.obuf, bo.fill);
-            if (fmt == NDFL_FMT_ZLIB) {                               // big-endian Adler-32
-                for (int k = 3; k >= 0; k--) bp.put((sum >> (8 * k)) & 0xFFu, 8);
-            } else {                                                  // CRC-32, ISIZE: little-endian
-                const uint32_t isz = (uint32_t)v_len;
-                for (int k = 0; k < 4; k++) bp.put((sum >> (8 * k)) & 0xFFu, 8);
-                for (int k = 0; k < 4; k++) bp.put((isz >> (8 * k)) & 0xFFu, 8);
-            }
-            bp.flush();
-        }
-        bo.fill += 8 * tl;
-        __syncthreads();
-        store_bytes(bo, bo.fill >> 3);
-        if (lane == 0) {
-            ndfl_deflate_result rr;
-            rr.out_len = bo.v_wbase + (bo.fill >> 3);
-            rr.status = rr.out_len > bo.v_cap ? NDFL_E_CAPACITY : 0;
-            rr.checksum = sum;
-            rr.end_bits = v_end_bits;
-            ((ndfl_deflate_result*)(uintptr_t)v_results)[v_si] = rr;
-        }
+        dbat::finish_stream(f, st, bo, v_fill);
     }
 }
 
@@ -431,37 +340,33 @@ struct BatchLzScratch {
 // at most 128 KiB of links and 256 KiB of tokens, so the budget never leaves fewer than 682 waves.
 constexpr size_t BATCH_LZ_BUDGET = (size_t)256 << 20;
 
-// deflate_batch_run's launcher for ndfl_deflate_batch_lz_kernel: sizes the wave's ring and token list from
-// the batch, lowers the grid to the budget, grows the scratch (first use only) and launches.
+// batch_run's launcher for ndfl_deflate_batch_lz_kernel.
 struct BatchLzLaunch {
     BatchLzScratch& Z;
     const Knobs& knobs;
     const ndfl_member_item* items;       // host
-    uint32_t n;
-    dblz::Args a;                         // the search parameters, chunk_len, hist_limit, dynamic, crc_tab
-    int operator()(hipStream_t s, const uint8_t* d_src, uint8_t* d_out, const ndfl_member_item* d_items,
-                   ndfl_deflate_result* d_res, uint32_t* d_ticket, hipEvent_t e0, hipEvent_t e1) {
+    dblz::Args a;                         // n, chunk_len, hist_limit, dynamic, the search parameters, crc_tab;
+                                          //   deflate_batch_run sets `in`
+    uint32_t grid = 0;
+    // Before the launch is timed: sizes the wave's ring and token list from the batch, lowers the grid to
+    // the budget and grows the scratch (first use only).
+    int prepare() {
         uint64_t longest = 0;
-        for (uint32_t i = 0; i < n; i++) longest = std::max(longest, items[i].in_len);
+        for (uint32_t i = 0; i < a.n; i++) longest = std::max(longest, items[i].in_len);
         uint32_t ring = 64;
         while (ring < dblz::RING_MAX && ring < longest) ring <<= 1;
-        const uint32_t tok_cap = (uint32_t)std::max<uint64_t>(64, std::min<uint64_t>(a.chunk_len, longest));
-        const size_t per_wave = (size_t)ring * 2 + (size_t)tok_cap * 4;
-        static const uint32_t auto_grid = wave_grid(ndfl_deflate_batch_lz_kernel, 256 * 16);
-        uint32_t grid = std::min(n, auto_grid);
-        if (knobs.batch_waves) grid = std::min(grid, knobs.batch_waves);
-        grid = (uint32_t)std::max<size_t>(1, std::min<size_t>(grid, BATCH_LZ_BUDGET / per_wave));
-        if (knobs.stats)
-            fprintf(stderr, "[ndfl] deflate batch lz77: %u streams, %u waves (of %u), %zu scratch bytes per wave\n", n, grid,
-                    auto_grid, per_wave);
+        a.tok_cap = (uint32_t)std::max<uint64_t>(64, std::min<uint64_t>(a.chunk_len, longest));
+        const size_t per_wave = (size_t)ring * 2 + (size_t)a.tok_cap * 4;
+        grid = batch_grid<ndfl_deflate_batch_lz_kernel>(a.n, knobs, "deflate batch lz77", per_wave, BATCH_LZ_BUDGET);
         INF_CHK(inf_ensure(&Z.d_mem, &Z.d_mem_cap, (size_t)grid * per_wave));
-        a.in = d_src; a.out = d_out; a.items = d_items; a.results = d_res; a.n = n; a.ticket = d_ticket;
-        a.toks = (uint32_t*)Z.d_mem; a.tok_cap = tok_cap;
-        a.ring = (uint16_t*)((char*)Z.d_mem + (size_t)grid * tok_cap * 4); a.ring_mask = ring - 1;
-        INF_CHK(hipEventRecord(e0, s));
+        a.toks = (uint32_t*)Z.d_mem;
+        a.ring = (uint16_t*)((char*)Z.d_mem + (size_t)grid * a.tok_cap * 4); a.ring_mask = ring - 1;
+        return 0;
+    }
+    int operator()(hipStream_t s, uint8_t* d_out, const ndfl_member_item* d_items, ndfl_deflate_result* d_res,
+                   uint32_t* d_ticket) {
+        a.out = d_out; a.items = d_items; a.results = d_res; a.ticket = d_ticket;
         hipLaunchKernelGGL(ndfl_deflate_batch_lz_kernel, dim3(grid), dim3(64), 0, s, a);
-        INF_CHK(hipGetLastError());
-        INF_CHK(hipEventRecord(e1, s));
         return 0;
     }
 };

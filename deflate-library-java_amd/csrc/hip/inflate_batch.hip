@@ -395,52 +395,55 @@ struct BatchScratch {
     }
 };
 
-// The batch on stream s (arguments already validated): one launch, one host sync.  results[i].status
-// comes back as the kernel wrote it (internal Reason codes; the C ABI maps them).  Host output goes
-// through a device staging buffer and only each stream's stored bytes are copied into `out`.
-// M: ndfl_inflate_members (its items, results and kernel; crc_x = the context's x^(8k) tables).
-template <bool M>
-static int inflate_batch_run(InflateScratch& S, BatchScratch& B, hipStream_t s, hipEvent_t e0, hipEvent_t e1,
-                             const uint8_t* in, uint64_t in_size, uint8_t* out, const typename bat::Io<M>::Item* items,
-                             typename bat::Io<M>::Result* results, uint32_t n, uint32_t flags, double* last_ms,
-                             const uint32_t* crc_x = nullptr) {
-    typedef typename bat::Io<M>::Item Item;
-    typedef typename bat::Io<M>::Result Result;
-    const uint32_t* d_w = nullptr;
-    INF_RC(stage_input(S, s, in, in_size, flags, &d_w));
+// The grid of a batch kernel (one-wave workgroups that claim streams from a ticket): what fits on the
+// chip at once, no more waves than streams, at most NDFL_BATCH_WAVES and, where every wave needs
+// per_wave bytes of device memory of its own, no more than `budget` bytes of it in all.  `label` names
+// the call in the NDFL_STATS line.
+template <auto Kernel>
+static uint32_t batch_grid(uint32_t n, const Knobs& knobs, const char* label, size_t per_wave = 0, size_t budget = 0) {
+    static const uint32_t auto_grid = wave_grid(Kernel, 256 * 16);
+    uint32_t grid = std::min(n, auto_grid);
+    if (knobs.batch_waves) grid = std::min(grid, knobs.batch_waves);
+    if (per_wave) grid = (uint32_t)std::max<size_t>(1, std::min<size_t>(grid, budget / per_wave));
+    if (knobs.stats) {
+        fprintf(stderr, "[ndfl] %s: %u streams, %u waves (of %u)", label, n, grid, auto_grid);
+        if (per_wave) fprintf(stderr, ", %zu scratch bytes per wave", per_wave);
+        fputc('\n', stderr);
+    }
+    return grid;
+}
+
+// One batch call on stream s (arguments already validated, input already staged): one launch, one host
+// sync.  The items, the results and the zeroed ticket share B.d_items.  Host output goes through the
+// device staging buffer B.d_out, which spans the items' regions, and only each stream's stored bytes
+// are copied into `out`.  launch(s, d_out, d_items, d_results, d_ticket) starts the kernel (d_out: the
+// kernel's `out`, item offsets are relative to it) and returns 0 or an error code; the time between the
+// two events around it becomes *last_ms, so the caller sizes the grid and whatever the kernel needs
+// allocated before it comes here.  results[i] comes back as the kernel wrote it.
+template <class Item, class Result, class Launch>
+static int batch_run(BatchScratch& B, hipStream_t s, hipEvent_t e0, hipEvent_t e1, uint8_t* out, const Item* items,
+                     Result* results, uint32_t n, uint32_t flags, double* last_ms, Launch&& launch) {
     const size_t items_b = (size_t)n * sizeof(Item), res_b = (size_t)n * sizeof(Result);
     INF_CHK(inf_ensure(&B.d_items, &B.d_items_cap, items_b + res_b + 16));
     Result* d_res = (Result*)((char*)B.d_items + items_b);
     uint32_t* d_ticket = (uint32_t*)((char*)d_res + res_b);
     INF_CHK(hipMemcpyAsync(B.d_items, items, items_b, hipMemcpyHostToDevice, s));
     INF_CHK(hipMemsetAsync(d_ticket, 0, 16, s));
-    // the span of `out` the regions cover (host output: staged on the device)
-    uint64_t lo = ~0ull, hi = 0;
+    uint64_t lo = ~0ull, hi = 0;                 // the span of `out` the regions cover
     for (uint32_t i = 0; i < n; i++) {
         if (!items[i].out_cap) continue;
         lo = std::min(lo, items[i].out_off);
         hi = std::max(hi, items[i].out_off + items[i].out_cap);
     }
     const bool out_dev = (flags & 2u) != 0;
-    uint8_t* d_out = out;                        // the kernel's `out` (item offsets are relative to it)
+    uint8_t* d_out = out;
     std::vector<uint8_t> h_span;
     if (!out_dev) {
         if (hi > lo) INF_CHK(inf_ensure(&B.d_out, &B.d_out_cap, hi - lo));
         d_out = (uint8_t*)B.d_out - (hi > lo ? lo : 0);
     }
-    static const uint32_t auto_grid = M ? wave_grid(ndfl_inflate_members_kernel, 256 * 16)
-                                        : wave_grid(ndfl_inflate_batch_kernel, 256 * 16);
-    uint32_t grid = std::min(n, auto_grid);
-    if (S.knobs.batch_waves) grid = std::min(grid, S.knobs.batch_waves);
-    if (S.knobs.stats) fprintf(stderr, "[ndfl] inflate %s: %u streams, %u waves (of %u)\n", M ? "members" : "batch", n, grid,
-                               auto_grid);
     INF_CHK(hipEventRecord(e0, s));
-    if constexpr (M)
-        hipLaunchKernelGGL(ndfl_inflate_members_kernel, dim3(grid), dim3(64), 0, s, d_w, d_out, (const Item*)B.d_items, d_res,
-                           n, d_ticket, crc_x);
-    else
-        hipLaunchKernelGGL(ndfl_inflate_batch_kernel, dim3(grid), dim3(64), 0, s, d_w, d_out, (const Item*)B.d_items, d_res,
-                           n, d_ticket);
+    INF_RC(launch(s, d_out, (const Item*)B.d_items, d_res, d_ticket));
     INF_CHK(hipGetLastError());
     INF_CHK(hipEventRecord(e1, s));
     INF_CHK(hipMemcpyAsync(results, d_res, res_b, hipMemcpyDeviceToHost, s));
@@ -458,3 +461,29 @@ static int inflate_batch_run(InflateScratch& S, BatchScratch& B, hipStream_t s, 
         }
     return 0;
 }
+
+// ndfl_inflate_batch (M = false) and ndfl_inflate_members (M = true: its items, results and kernel; crc_x =
+// the context's x^(8k) tables).  results[i].status holds the internal Reason codes; the C ABI maps them.
+template <bool M>
+static int inflate_batch_run(InflateScratch& S, BatchScratch& B, hipStream_t s, hipEvent_t e0, hipEvent_t e1,
+                             const uint8_t* in, uint64_t in_size, uint8_t* out, const typename bat::Io<M>::Item* items,
+                             typename bat::Io<M>::Result* results, uint32_t n, uint32_t flags, double* last_ms,
+                             const uint32_t* crc_x = nullptr) {
+    typedef typename bat::Io<M>::Item Item;
+    typedef typename bat::Io<M>::Result Result;
+    const uint32_t* d_w = nullptr;
+    INF_RC(stage_input(S, s, in, in_size, flags, &d_w));
+    const uint32_t grid = M ? batch_grid<ndfl_inflate_members_kernel>(n, S.knobs, "inflate members")
+                            : batch_grid<ndfl_inflate_batch_kernel>(n, S.knobs, "inflate batch");
+    return batch_run(B, s, e0, e1, out, items, results, n, flags, last_ms,
+                     [&](hipStream_t q, uint8_t* d_out, const Item* d_items, Result* d_res, uint32_t* d_ticket) {
+        if constexpr (M)
+            hipLaunchKernelGGL(ndfl_inflate_members_kernel, dim3(grid), dim3(64), 0, q, d_w, d_out, d_items, d_res, n,
+                               d_ticket, crc_x);
+        else
+            hipLaunchKernelGGL(ndfl_inflate_batch_kernel, dim3(grid), dim3(64), 0, q, d_w, d_out, d_items, d_res, n,
+                               d_ticket);
+        return 0;
+    });
+}
+

@@ -353,24 +353,23 @@ class Context:
         reserved symbol."""
         return DataFormatException(Reason(result[0] - 1), symbol=result[1])
 
-    def inflate_batch_raw(self, in_addr, in_size, out_addr, out_size, items, flags):
-        """ndfl_inflate_batch: `items` is a sequence of (in_off, in_len, out_off, out_cap).  Returns one
-        (code, error_symbol, out_len, consumed_bits) per stream; code = 0 / Reason+1 / E_CAPACITY."""
-        L = load()
+    def _batch_raw(self, name, item_type, result_type, fields, in_addr, in_size, out_addr, out_size, items, *rest):
+        """One batch entry point `name`: `items` marshalled as item_type, `rest` = its arguments after n
+        (one given as a function is evaluated once the items are marshalled).  Returns the `fields` of
+        every stream's result_type as a tuple."""
         self._order()
         n = len(items)
-        arr = (_lib.BatchItem * max(1, n))(*[_lib.BatchItem(*map(int, it)) for it in items])
-        res = (_lib.BatchResult * max(1, n))()
-        check(L.ndfl_inflate_batch(self._h, in_addr, in_size, out_addr, out_size, arr, res, n, flags),
-              "ndfl_inflate_batch")
-        return [(r.status, r.error_symbol, r.out_len, r.consumed_bits) for r in res[:n]]
+        arr = (item_type * max(1, n))(*[item_type(*map(int, it)) for it in items])
+        res = (result_type * max(1, n))()
+        rest = [a() if callable(a) else a for a in rest]
+        check(getattr(load(), name)(self._h, in_addr, in_size, out_addr, out_size, arr, res, n, *rest), name)
+        return [tuple(getattr(r, f) for f in fields) for r in res[:n]]
 
-    def inflate_batch(self, streams, out_caps=None):
-        """Decode many independent raw DEFLATE streams (host bytes) in one call.  Returns one
-        (reason|None, bytes, consumed_bits) per stream.  With out_caps (one capacity per stream) a stream
-        that needs more raises NdflError(E_CAPACITY); without, every region is 4 * len + 65536 bytes and
-        only the streams that overflowed are run again, with the size they reported."""
-        streams = [bytes(s) for s in streams]
+    def _inflate_packed(self, raw, name, streams, more, out_caps):
+        """inflate_batch / inflate_members: the streams packed back to back and run through `raw` (entry
+        point `name`); without out_caps the streams that overflowed are run again with the size they
+        reported.  more[i]: stream i's item fields after out_cap.  Returns (reason|None, bytes) followed
+        by the result's fields after out_len, per stream."""
         n = len(streams)
         done = [None] * n
         todo = list(range(n))
@@ -380,36 +379,47 @@ class Context:
             src = ctypes.create_string_buffer(packed, max(1, len(packed)))
             items, in_off, out_off = [], 0, 0
             for i in todo:
-                items.append((in_off, len(streams[i]), out_off, caps[i]))
+                items.append((in_off, len(streams[i]), out_off, caps[i]) + tuple(more[i]))
                 in_off += len(streams[i])
                 out_off += caps[i]
             out = ctypes.create_string_buffer(max(1, out_off))
-            res = self.inflate_batch_raw(ctypes.addressof(src), len(packed), ctypes.addressof(out), out_off, items, 0)
+            res = raw(ctypes.addressof(src), len(packed), ctypes.addressof(out), out_off, items, 0)
             again = []
             for i, it, r in zip(todo, items, res):
-                code, _, olen, bits = r
+                code, olen = r[0], r[2]
                 if code == _lib.E_CAPACITY and out_caps is None:
                     caps[i] = olen
                     again.append(i)
                     continue
-                check(code, "ndfl_inflate_batch")
-                done[i] = (None if code == 0 else Reason(code - 1), ctypes.string_at(ctypes.addressof(out) + it[2], min(olen, it[3])), bits)
+                check(code, name)
+                done[i] = (None if code == 0 else Reason(code - 1),
+                           ctypes.string_at(ctypes.addressof(out) + it[2], min(olen, it[3]))) + tuple(r[3:])
             todo = again
         return done
+
+    def inflate_batch_raw(self, in_addr, in_size, out_addr, out_size, items, flags):
+        """ndfl_inflate_batch: `items` is a sequence of (in_off, in_len, out_off, out_cap).  Returns one
+        (code, error_symbol, out_len, consumed_bits) per stream; code = 0 / Reason+1 / E_CAPACITY."""
+        return self._batch_raw("ndfl_inflate_batch", _lib.BatchItem, _lib.BatchResult,
+                               ("status", "error_symbol", "out_len", "consumed_bits"),
+                               in_addr, in_size, out_addr, out_size, items, flags)
+
+    def inflate_batch(self, streams, out_caps=None):
+        """Decode many independent raw DEFLATE streams (host bytes) in one call.  Returns one
+        (reason|None, bytes, consumed_bits) per stream.  With out_caps (one capacity per stream) a stream
+        that needs more raises NdflError(E_CAPACITY); without, every region is 4 * len + 65536 bytes and
+        only the streams that overflowed are run again, with the size they reported."""
+        streams = [bytes(s) for s in streams]
+        return self._inflate_packed(self.inflate_batch_raw, "ndfl_inflate_batch", streams, [()] * len(streams), out_caps)
 
     def inflate_members_raw(self, in_addr, in_size, out_addr, out_size, items, flags):
         """ndfl_inflate_members: `items` is a sequence of (in_off, in_len, out_off, out_cap, format, sum)
         with format a FMT_* and sum a SUM_* (read for FMT_RAW only).  Returns one (code, error_symbol,
         out_len, consumed_bits, checksum, header_len) per stream; code = 0 / Reason+1 / E_CAPACITY /
         E_ARG (a zlib header whose CINFO the reference's ZlibMetadata refuses)."""
-        L = load()
-        self._order()
-        n = len(items)
-        arr = (_lib.MemberItem * max(1, n))(*[_lib.MemberItem(*map(int, it)) for it in items])
-        res = (_lib.MemberResult * max(1, n))()
-        check(L.ndfl_inflate_members(self._h, in_addr, in_size, out_addr, out_size, arr, res, n, flags),
-              "ndfl_inflate_members")
-        return [(r.status, r.error_symbol, r.out_len, r.consumed_bits, r.checksum, r.header_len) for r in res[:n]]
+        return self._batch_raw("ndfl_inflate_members", _lib.MemberItem, _lib.MemberResult,
+                               ("status", "error_symbol", "out_len", "consumed_bits", "checksum", "header_len"),
+                               in_addr, in_size, out_addr, out_size, items, flags)
 
     def inflate_members(self, streams, format, sum=None, out_caps=None):
         """Decode many zlib members (FMT_ZLIB), gzip members (FMT_GZIP: one member per stream) or raw
@@ -420,66 +430,34 @@ class Context:
         needs more raises NdflError(E_CAPACITY); without, every region is 4 * len + 65536 bytes and only
         the streams that overflowed are run again, with the size they reported."""
         streams = [bytes(s) for s in streams]
-        n = len(streams)
-        fmts = [int(format)] * n if isinstance(format, int) else [int(f) for f in format]
+        fmts = [int(format)] * len(streams) if isinstance(format, int) else [int(f) for f in format]
         kind = _lib.SUM_NONE if sum is None else int(sum)
-        done = [None] * n
-        todo = list(range(n))
-        caps = [4 * len(s) + 65536 for s in streams] if out_caps is None else [int(c) for c in out_caps]
-        while todo:
-            packed = b"".join(streams[i] for i in todo)
-            src = ctypes.create_string_buffer(packed, max(1, len(packed)))
-            items, in_off, out_off = [], 0, 0
-            for i in todo:
-                items.append((in_off, len(streams[i]), out_off, caps[i], fmts[i], kind))
-                in_off += len(streams[i])
-                out_off += caps[i]
-            out = ctypes.create_string_buffer(max(1, out_off))
-            res = self.inflate_members_raw(ctypes.addressof(src), len(packed), ctypes.addressof(out), out_off, items, 0)
-            again = []
-            for i, it, r in zip(todo, items, res):
-                code, _, olen, bits, checksum, header_len = r
-                if code == _lib.E_CAPACITY and out_caps is None:
-                    caps[i] = olen
-                    again.append(i)
-                    continue
-                check(code, "ndfl_inflate_members")
-                done[i] = (None if code == 0 else Reason(code - 1),
-                           ctypes.string_at(ctypes.addressof(out) + it[2], min(olen, it[3])), bits, checksum, header_len)
-            todo = again
-        return done
+        return self._inflate_packed(self.inflate_members_raw, "ndfl_inflate_members", streams,
+                                    [(f, kind) for f in fmts], out_caps)
+
+    _DEFLATE_RESULT = ("status", "checksum", "out_len", "end_bits")
 
     def deflate_batch_raw(self, in_addr, in_size, out_addr, out_size, items, strategy, chunk_len, hist_limit, flags):
         """ndfl_deflate_batch: `items` is a sequence of (in_off, in_len, out_off, out_cap, format, sum):
         item i's raw bytes, the region of its compressed member, its container (FMT_*) and, for FMT_RAW,
         the checksum wanted (SUM_*).  Returns one (status, checksum, out_len, end_bits) per stream; status
         = 0 / E_CAPACITY."""
-        L = load()
-        self._order()
-        n = len(items)
-        arr = (_lib.MemberItem * max(1, n))(*[_lib.MemberItem(*map(int, it)) for it in items])
-        res = (_lib.DeflateResult * max(1, n))()
-        sid = _strategy_id(strategy)
-        if not isinstance(sid, int):                 # (strategy objects: only the presets are batched)
-            raise NdflError(_lib.E_UNSUPPORTED, "ndfl_deflate_batch")
-        check(L.ndfl_deflate_batch(self._h, in_addr, in_size, out_addr, out_size, arr, res, n, sid,
-                                   chunk_len, hist_limit, flags), "ndfl_deflate_batch")
-        return [(r.status, r.checksum, r.out_len, r.end_bits) for r in res[:n]]
+        def sid():
+            v = _strategy_id(strategy)
+            if not isinstance(v, int):               # (strategy objects: only the presets are batched)
+                raise NdflError(_lib.E_UNSUPPORTED, "ndfl_deflate_batch")
+            return v
+        return self._batch_raw("ndfl_deflate_batch", _lib.MemberItem, _lib.DeflateResult, self._DEFLATE_RESULT,
+                               in_addr, in_size, out_addr, out_size, items, sid, chunk_len, hist_limit, flags)
 
     def deflate_batch_lz77_raw(self, in_addr, in_size, out_addr, out_size, items, dynamic, min_run, max_run, min_dist,
                                max_dist, chunk_len, hist_limit, flags):
         """ndfl_deflate_batch_lz77: deflate_batch_raw with Lz77Huffman(dynamic, min_run, max_run, min_dist,
         max_dist) as the strategy; the same items and the same (status, checksum, out_len, end_bits) per
         stream."""
-        L = load()
-        self._order()
-        n = len(items)
-        arr = (_lib.MemberItem * max(1, n))(*[_lib.MemberItem(*map(int, it)) for it in items])
-        res = (_lib.DeflateResult * max(1, n))()
-        check(L.ndfl_deflate_batch_lz77(self._h, in_addr, in_size, out_addr, out_size, arr, res, n, int(dynamic),
-                                        min_run, max_run, min_dist, max_dist, chunk_len, hist_limit, flags),
-              "ndfl_deflate_batch_lz77")
-        return [(r.status, r.checksum, r.out_len, r.end_bits) for r in res[:n]]
+        return self._batch_raw("ndfl_deflate_batch_lz77", _lib.MemberItem, _lib.DeflateResult, self._DEFLATE_RESULT,
+                               in_addr, in_size, out_addr, out_size, items, int(dynamic), min_run, max_run, min_dist,
+                               max_dist, chunk_len, hist_limit, flags)
 
     def _deflate_packed(self, buffers, fmt, kind, headers, strategy, chunk_len, hist_limit):
         """One batch over host buffers: each region is its header's bytes (the caller's part of a

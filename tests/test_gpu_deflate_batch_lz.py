@@ -20,11 +20,11 @@ import zlib
 
 import pytest
 
-import knobs
+import deflate_batch_harness as H
 import oracle_lib as O
 import test_gpu_lz77 as LZ
-from test_gpu_deflate_batch import (ADLER32, CRC32, E_ARG, E_CAPACITY, E_UNSUPPORTED, FILL, GZIP, NONE, RAW, ZLIB,
-                                    checksum, mixed, pack_inputs, salad, trailer)
+from deflate_batch_harness import (ADLER32, CRC32, E_ARG, E_CAPACITY, E_UNSUPPORTED, FILL, GZIP, NONE, RAW, ZLIB,
+                                   checksum, ctx, mixed, one_wave, pack_inputs, salad, trailer)  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -32,23 +32,6 @@ FULL_DYNAMIC = (True, 3, 258, 1, 32768)
 FULL_STATIC = (False, 3, 258, 1, 32768)
 DEFAULT = (FULL_DYNAMIC, 65536, 32768)
 STEP = 64                         # positions per step (deflate_batch_lz.hip)
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import torch
-    import ndfl
-    c = ndfl.Context(0)
-    c.set_stream(torch.cuda.current_stream().cuda_stream)     # ordered with torch's kernels
-    return c
-
-
-@pytest.fixture(scope="module")
-def one_wave():
-    import torch
-    c = knobs.context(NDFL_BATCH_WAVES=1)
-    c.set_stream(torch.cuda.current_stream().cuda_stream)
-    return c
 
 
 @functools.lru_cache(maxsize=None)
@@ -60,61 +43,16 @@ def oracle(buf, params=FULL_DYNAMIC, chunk_len=65536, hist_limit=32768):
     return comp, bits
 
 
-def member(buf, fmt, cfg):
-    comp, bits = oracle(buf, *cfg)
-    return comp + trailer(buf, fmt), bits
-
-
-def run(ctx, items, cfg, regions=None, caps=None, out_size=None, out_shift=0, inputs=None):
-    """One ndfl_deflate_batch_lz77 call on host buffers, as test_gpu_deflate_batch.run: items are (buffer,
-    format, sum), cfg is (params, chunk_len, hist_limit), regions default to touching ones of caps[i]
-    (default: the member's length) bytes.  Returns (results, out bytes, regions)."""
-    if regions is None:
-        regions, off = [], 0
-        for i, (buf, fmt, _) in enumerate(items):
-            cap = caps[i] if caps is not None else len(member(buf, fmt, cfg)[0])
-            regions.append((off, cap))
-            off += cap
-    if out_size is None:
-        out_size = max([o + c for o, c in regions] + [1])
-    packed, offs = inputs if inputs is not None else pack_inputs(items)
-    recs = [(io, len(buf), o, c, fmt, kind) for (buf, fmt, kind), io, (o, c) in zip(items, offs, regions)]
-    src = ctypes.create_string_buffer(packed, max(1, len(packed)))
-    out = ctypes.create_string_buffer(bytes([FILL]) * (out_size + out_shift), out_size + out_shift)
+def raw(ctx, in_addr, in_size, out_addr, out_size, recs, cfg, flags):
+    """ndfl_deflate_batch_lz77; cfg: (params, chunk_len, hist_limit)."""
     params, chunk_len, hist_limit = cfg
-    res = ctx.deflate_batch_lz77_raw(ctypes.addressof(src), len(packed), ctypes.addressof(out) + out_shift, out_size,
-                                     recs, *params, chunk_len, hist_limit, 0)
-    assert out.raw[:out_shift] == bytes([FILL]) * out_shift
-    return res, out.raw[out_shift:], regions
+    return ctx.deflate_batch_lz77_raw(in_addr, in_size, out_addr, out_size, recs, *params, chunk_len, hist_limit, flags)
 
 
-def check(items, cfg, res, out, regions, what=""):
-    """Every stream against the oracle (the first min(out_len, cap) bytes are stored), the zero high bits
-    of its last DEFLATE byte, and every other byte of `out` still FILL."""
-    expect = bytearray(bytes([FILL]) * len(out))
-    for i, ((buf, fmt, kind), r, (off, cap)) in enumerate(zip(items, res, regions)):
-        exp, bits = member(buf, fmt, cfg)
-        status, ck, olen, end_bits = r
-        where = (what, cfg, i, len(buf), off, cap)
-        assert status == (E_CAPACITY if len(exp) > cap else 0), (where, status)
-        assert olen == len(exp), (where, olen, len(exp))
-        assert end_bits == bits, (where, end_bits, bits)
-        assert ck == checksum(buf, fmt, kind), (where, ck)
-        last = exp[(bits + 7) // 8 - 1]
-        assert bits % 8 == 0 or last >> (bits % 8) == 0, where
-        n = min(len(exp), cap)
-        expect[off:off + n] = exp[:n]
-    if out != bytes(expect):
-        bad = next(k for k in range(len(out)) if out[k] != expect[k])
-        owner = [i for i, (off, cap) in enumerate(regions) if off <= bad < off + cap]
-        raise AssertionError((what, cfg, "first wrong byte", bad, "region of stream", owner,
-                              [len(items[i][0]) for i in owner], out[bad], expect[bad]))
-
-
-def run_check(ctx, items, cfg, what="", **kw):
-    res, out, regions = run(ctx, items, cfg, **kw)
-    check(items, cfg, res, out, regions, what)
-    return res
+member = functools.partial(H.member, oracle)
+run = functools.partial(H.run, raw, oracle)
+check = functools.partial(H.check, oracle)
+run_check = functools.partial(H.run_check, raw, oracle)
 
 
 def raws(bufs):
