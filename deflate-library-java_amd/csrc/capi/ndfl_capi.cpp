@@ -9,6 +9,7 @@
 #include "../hip/inflate_batch.hip"
 #include "../hip/deflate_batch.hip"
 #include "../hip/deflate_batch_lz.hip"
+#include "../hip/deflate_batch_multi.hip"
 
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -78,7 +79,7 @@ struct ndfl_ctx {
     uint32_t parent_len = 0;        // internal: history rule of BinarySplit sub-blocks (0: chunk_len)
     InflateScratch inf;
     BatchScratch batch;             // ndfl_inflate_batch: items / results / host-output staging
-    BatchLzScratch batch_lz;        // ndfl_deflate_batch_lz77: the waves' link rings and token lists
+    BatchLzScratch batch_lz;        // ndfl_deflate_batch_lz77 / _multi: the waves' link rings and token lists
     uint32_t* h_pinned = nullptr;   // small pinned area for results
     Knobs knobs;                    // switches read once at ndfl_ctx_create (ndfl_common.hpp)
     int err_sym = -1;               // the last decode's reserved symbol (ndfl_ctx_error_symbol), or -1
@@ -1143,6 +1144,38 @@ int ndfl_deflate_batch_lz77(ndfl_ctx* c, const uint8_t* in, uint64_t in_size, ui
     launch.a.n = n; launch.a.chunk_len = chunk_len; launch.a.hist_limit = hist_limit; launch.a.dynamic = dynamic != 0;
     launch.a.min_run = (uint32_t)min_run; launch.a.max_run = (uint32_t)max_run;
     launch.a.min_dist = (uint32_t)min_dist; launch.a.max_dist = (uint32_t)max_dist;
+    launch.a.crc_tab = c->d_tabs.as<uint32_t>();
+    return batch_status(deflate_batch_run(c->batch, &c->d_in.p, &c->d_in.cap, ordered_stream(c), c->ev0, c->ev1, in, out,
+                                          items, results, n, flags, launch, &c->last_ms));
+}
+
+int ndfl_deflate_batch_multi(ndfl_ctx* c, const uint8_t* in, uint64_t in_size, uint8_t* out, uint64_t out_size,
+                             const ndfl_member_item* items, ndfl_deflate_result* results, uint32_t n,
+                             const ndfl_strategy_desc* strats, uint32_t n_strats, uint32_t chunk_len,
+                             uint32_t hist_limit, uint32_t flags) {
+    if (!c) return NDFL_E_ARG;
+    if (n == 0) return NDFL_OK;
+    if (!strats || n_strats == 0) return NDFL_E_ARG;                                            // (D/comp/MultiStrategy.java:25-26)
+    if (n_strats > dbm::MAXC) return NDFL_E_UNSUPPORTED;
+    for (uint32_t k = 0; k < n_strats; k++) {                       // as ndfl_deflate_chunks_multi
+        const ndfl_strategy_desc& d = strats[k];
+        if (d.kind == NDFL_KIND_UNCOMPRESSED) continue;
+        if (d.kind != NDFL_KIND_LZ77) return NDFL_E_ARG;
+        const bool lit = d.min_run == 0 && d.max_run == 0 && d.min_dist == 0 && d.max_dist == 0;
+        if (!lit && !(3 <= d.min_run && d.min_run <= d.max_run && d.max_run <= 258 && 1 <= d.min_dist &&
+                      d.min_dist <= d.max_dist && d.max_dist <= 32768))
+            return NDFL_E_ARG;
+    }
+    BatchMultiLaunch launch{c->batch_lz, c->knobs, items, dbm::Args{}};
+    // one Lz77Huffman alone, or several equal ones: nothing to choose, ndfl_deflate_batch_lz77's stream
+    if (launch.set_candidates(strats, n_strats) == 1 && !(launch.a.c_flags[0] & dbm::C_STORED)) {
+        const ndfl_strategy_desc& d = strats[launch.a.c_flags[0] >> 8];
+        return ndfl_deflate_batch_lz77(c, in, in_size, out, out_size, items, results, n, d.dynamic, d.min_run, d.max_run,
+                                       d.min_dist, d.max_dist, chunk_len, hist_limit, flags);
+    }
+    if (const int e = deflate_batch_args(in, in_size, out, out_size, items, results, n, chunk_len, hist_limit)) return e;
+    HIPCHK(hipSetDevice(c->device));
+    launch.a.n = n; launch.a.chunk_len = chunk_len; launch.a.hist_limit = hist_limit;
     launch.a.crc_tab = c->d_tabs.as<uint32_t>();
     return batch_status(deflate_batch_run(c->batch, &c->d_in.p, &c->d_in.cap, ordered_stream(c), c->ev0, c->ev1, in, out,
                                           items, results, n, flags, launch, &c->last_ms));

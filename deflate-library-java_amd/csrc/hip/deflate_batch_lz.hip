@@ -105,6 +105,14 @@ __device__ __forceinline__ void fold_chunk(uint64_t v_tab, const uint8_t* cp, ui
 // stream's end, or a few bytes past the chunk's).  hsm = (uint32_t)hs: the ring slot of position r is
 // (hsm + r) & mask.  cb = cs - the head table's base, carried from chunk to chunk.  Returns the number
 // of tokens stored in toks[].
+// PART: the whole of it (LZ_ALL), or one of its two halves for a caller that searches a chunk more than
+// once (deflate_batch_multi.hip): LZ_LINK links the chunk's positions (head table, ring, rebase; cb is
+// used and nothing else, returns 0), LZ_SEARCH searches and parses a chunk whose positions are all linked
+// already (cb is not used).  Linking a chunk twice would link its positions to their own later entries
+// in the head table.  With the whole chunk linked before its first position is searched, the ring must
+// hold the chunk and its window at once: mask + 1 >= min(the stream, hist_limit + the chunk's length).
+constexpr int LZ_ALL = 0, LZ_LINK = 1, LZ_SEARCH = 2;
+template <int PART = LZ_ALL>
 __device__ __forceinline__ uint32_t lz_chunk(Lds& S, const Search& sp, const uint8_t* P, uint32_t rc0, uint32_t len_c,
                                              uint32_t rend, uint32_t hsm, uint16_t* ring, uint32_t mask, uint32_t* toks,
                                              bool dyn, uint32_t& cb) {
@@ -115,41 +123,51 @@ __device__ __forceinline__ uint32_t lz_chunk(Lds& S, const Search& sp, const uin
         const uint32_t t = sb + (uint32_t)lane;
         const bool inb = t < len_c;
         const uint32_t ri = rc0 + t;
-        if (cb + sb >= REBASE_AT) {           // (a step adds 64: one move keeps cb + sb below REBASE_AT)
-            for (uint32_t k = (uint32_t)lane; k < NHEAD; k += 64) {
-                const uint32_t v = S.head[k];
-                S.head[k] = (uint16_t)((v != HNONE && v >= REBASE) ? v - REBASE : HNONE);
+        if constexpr (PART != LZ_SEARCH) {
+            if (cb + sb >= REBASE_AT) {       // (a step adds 64: one move keeps cb + sb below REBASE_AT)
+                for (uint32_t k = (uint32_t)lane; k < NHEAD; k += 64) {
+                    const uint32_t v = S.head[k];
+                    S.head[k] = (uint16_t)((v != HNONE && v >= REBASE) ? v - REBASE : HNONE);
+                }
+                cb -= REBASE;
+                __syncthreads();
             }
-            cb -= REBASE;
-            __syncthreads();
         }
         // ---- link: the stream's last two positions have no 3-byte prefix and are not linked -------
         const uint32_t wi0 = inb ? ld4(P, ri, rend) : 0u;
-        const bool hasp = inb && ri + 2 < rend;
-        uint32_t h = 0x10000u + (uint32_t)lane;                   // a bucket of its own
-        if (hasp) h = hash3(wi0 & 0xFFFFFFu);
-        int prevLane = -1;
-        bool last = true;
-#pragma unroll 8
-        for (int k = 0; k < 64; k++) {
-            const uint32_t hk = (uint32_t)__builtin_amdgcn_readlane((int)h, k);
-            const bool eq = hk == h;
-            if (eq && k < lane) prevLane = k;
-            if (eq && k > lane) last = false;
-        }
-        const uint32_t off = cb + t;
         uint32_t d = 0;
-        if (hasp) {
-            if (prevLane >= 0) {
-                d = (uint32_t)(lane - prevLane);
-            } else {
-                const uint32_t hv = S.head[h];
-                if (hv != HNONE) { d = off - hv; if (d > MAXD) d = 0; }
+        if constexpr (PART != LZ_SEARCH) {
+            const bool hasp = inb && ri + 2 < rend;
+            uint32_t h = 0x10000u + (uint32_t)lane;               // a bucket of its own
+            if (hasp) h = hash3(wi0 & 0xFFFFFFu);
+            int prevLane = -1;
+            bool last = true;
+            // (every compare below is a lane mask in a scalar pair.  LZ_LINK is inlined into a kernel with
+            // more live scalar state than this file's: keep its scan at 4, or that kernel spills SGPRs)
+            constexpr int UNROLL = PART == LZ_LINK ? 4 : 8;
+#pragma unroll UNROLL
+            for (int k = 0; k < 64; k++) {
+                const uint32_t hk = (uint32_t)__builtin_amdgcn_readlane((int)h, k);
+                const bool eq = hk == h;
+                if (eq && k < lane) prevLane = k;
+                if (eq && k > lane) last = false;
             }
+            const uint32_t off = cb + t;
+            if (hasp) {
+                if (prevLane >= 0) {
+                    d = (uint32_t)(lane - prevLane);
+                } else {
+                    const uint32_t hv = S.head[h];
+                    if (hv != HNONE) { d = off - hv; if (d > MAXD) d = 0; }
+                }
+            }
+            if (hasp && last) S.head[h] = (uint16_t)off;          // (one wave: after every lane's read above)
+            if (inb) ring[(hsm + ri) & mask] = (uint16_t)d;
+            __syncthreads();                                      // the step's links, for every lane
+            if constexpr (PART == LZ_LINK) continue;
+        } else {
+            if (inb) d = ring[(hsm + ri) & mask];                 // (linked before: the caller's LZ_LINK pass)
         }
-        if (hasp && last) S.head[h] = (uint16_t)off;              // (one wave: after every lane's read above)
-        if (inb) ring[(hsm + ri) & mask] = (uint16_t)d;
-        __syncthreads();                                          // the step's links, for every lane
         // ---- search (ndfl_lz_match_kernel's walk) --------------------------------------------------
         // The walk reads link[rj] for rlo <= rj <= ri only.  Those positions are this stream's, all of
         // them linked by now (the stream is linked in order, this step included), and none of their
@@ -338,6 +356,8 @@ struct BatchLzScratch {
 
 // The most device memory the rings and token lists may take; the grid is lowered to fit.  A wave needs
 // at most 128 KiB of links and 256 KiB of tokens, so the budget never leaves fewer than 682 waves.
+// deflate_batch_multi.hip's BatchMultiLaunch shares the scratch and the budget: a wave of its kernel
+// needs at most 256 KiB of links and two token lists of 256 KiB, so never fewer than 341 waves.
 constexpr size_t BATCH_LZ_BUDGET = (size_t)256 << 20;
 
 // batch_run's launcher for ndfl_deflate_batch_lz_kernel.

@@ -459,17 +459,47 @@ class Context:
                                in_addr, in_size, out_addr, out_size, items, int(dynamic), min_run, max_run, min_dist,
                                max_dist, chunk_len, hist_limit, flags)
 
+    def deflate_batch_multi_raw(self, in_addr, in_size, out_addr, out_size, items, subs, chunk_len, hist_limit, flags):
+        """ndfl_deflate_batch_multi: deflate_batch_raw with MultiStrategy(subs...) as the strategy, `subs` a
+        sequence of Lz77Huffman / Uncompressed.SINGLETON (or ready-made _lib.StrategyDesc records); the
+        same items and the same (status, checksum, out_len, end_bits) per stream."""
+        descs = [x if isinstance(x, _lib.StrategyDesc) else _desc(x) for x in subs]
+        arr = (_lib.StrategyDesc * max(1, len(descs)))(*descs)
+        return self._batch_raw("ndfl_deflate_batch_multi", _lib.MemberItem, _lib.DeflateResult, self._DEFLATE_RESULT,
+                               in_addr, in_size, out_addr, out_size, items, arr, len(descs), chunk_len, hist_limit,
+                               flags)
+
+    @staticmethod
+    def _batch_subs(strategy):
+        """The substrategies ndfl_deflate_batch_multi takes for `strategy` (Uncompressed.SINGLETON, or a
+        MultiStrategy over a flat list of at most 8 Lz77Huffman / Uncompressed), None for the strategies
+        of the other two batch calls; any other MultiStrategy is not batched."""
+        if isinstance(strategy, _UncompressedType):
+            return (strategy,)
+        if not isinstance(strategy, MultiStrategy):
+            return None
+        subs = strategy.substrategies
+        if len(subs) > 8 or not all(isinstance(x, (Lz77Huffman, _UncompressedType)) for x in subs):
+            raise NdflError(_lib.E_UNSUPPORTED, "ndfl_deflate_batch_multi")
+        return subs
+
     def _deflate_packed(self, buffers, fmt, kind, headers, strategy, chunk_len, hist_limit):
         """One batch over host buffers: each region is its header's bytes (the caller's part of a
         container) followed by room for ndfl_deflate_bound(len) bytes and the trailer.  Returns one
         (bytes from the header on, end_bits, checksum) per buffer."""
         L = load()
         buffers = [bytes(b) for b in buffers]
+        subs = self._batch_subs(strategy)
         packed = b"".join(buffers)
         src = ctypes.create_string_buffer(packed, max(1, len(packed)))
         items, regions, in_off, out_off = [], [], 0, 0
         for b, h in zip(buffers, headers):
-            cap = L.ndfl_deflate_bound(len(b), chunk_len) * (2 if isinstance(strategy, Lz77Huffman) else 1) + 8
+            cap = L.ndfl_deflate_bound(len(b), chunk_len) * (2 if isinstance(strategy, Lz77Huffman) or subs else 1) + 8
+            if subs:
+                # the larger of that and the stored size (5 bytes a block, two blocks for a 65,536-byte
+                # chunk), and a byte per chunk for the bits the choice depends on the bit position by
+                chunks = max(1, -(-len(b) // max(1, chunk_len)))
+                cap = max(cap, len(b) + 5 * chunks * (2 if chunk_len > 65535 else 1) + 8) + chunks
             items.append((in_off, len(b), out_off + len(h), cap, fmt, kind))
             regions.append(out_off)
             in_off += len(b)
@@ -477,7 +507,10 @@ class Context:
         out = ctypes.create_string_buffer(max(1, out_off))
         for at, h in zip(regions, headers):
             ctypes.memmove(ctypes.addressof(out) + at, bytes(h), len(h))
-        if isinstance(strategy, Lz77Huffman):        # (a preset's name or id keeps ndfl_deflate_batch)
+        if subs:
+            res = self.deflate_batch_multi_raw(ctypes.addressof(src), len(packed), ctypes.addressof(out), out_off, items,
+                                               subs, chunk_len, hist_limit, 0)
+        elif isinstance(strategy, Lz77Huffman):      # (a preset's name or id keeps ndfl_deflate_batch)
             res = self.deflate_batch_lz77_raw(ctypes.addressof(src), len(packed), ctypes.addressof(out), out_off, items,
                                               strategy.useDynamicHuffmanCodes, *strategy.params, chunk_len, hist_limit, 0)
         else:
@@ -493,7 +526,9 @@ class Context:
     def deflate_batch(self, buffers, strategy=Strategy.RLE_DYNAMIC, chunk_len=65536, hist_limit=32768, sum=None):
         """Compress many independent host buffers in one call, each as deflate() compresses it alone
         (RLE_* / LITERAL_* presets by name or id through ndfl_deflate_batch; an Lz77Huffman instance, FULL_*
-        among them, through ndfl_deflate_batch_lz77).  Returns one (bytes, end_bits, checksum) per buffer; checksum is
+        among them, through ndfl_deflate_batch_lz77; Uncompressed.SINGLETON, or a MultiStrategy over a flat
+        list of at most 8 Lz77Huffman / Uncompressed, through ndfl_deflate_batch_multi; any other
+        MultiStrategy raises NdflError(E_UNSUPPORTED)).  Returns one (bytes, end_bits, checksum) per buffer; checksum is
         the buffer's CRC-32 / Adler-32 with sum = SUM_CRC32 / SUM_ADLER32, else 0."""
         buffers = list(buffers)
         kind = _lib.SUM_NONE if sum is None else int(sum)

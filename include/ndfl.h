@@ -358,7 +358,8 @@ int ndfl_inflate_members(ndfl_ctx* ctx, const uint8_t* in, uint64_t in_size, uin
  * payloads, zip entries, small gzip members).
  *   strategy    NDFL_LITERAL_STATIC, NDFL_LITERAL_DYNAMIC, NDFL_RLE_STATIC or NDFL_RLE_DYNAMIC.
  *               NDFL_FULL_* and NDFL_UNCOMPRESSED return NDFL_E_UNSUPPORTED for the call and nothing is
- *               written (the LZ77 match search takes one history start per call; not batched).
+ *               written: the LZ77 search is ndfl_deflate_batch_lz77's, Uncompressed and a per-chunk choice
+ *               among several strategies ndfl_deflate_batch_multi's.
  *   chunk_len   1..65536 (0: NDFL_E_ARG; above 65536: NDFL_E_UNSUPPORTED, as ndfl_deflate_chunks)
  *   hist_limit  0..32768, else NDFL_E_ARG
  *   format      NDFL_FMT_*.  A container's header does not depend on the data and is the caller's, written
@@ -443,6 +444,58 @@ int ndfl_deflate_batch_lz77(ndfl_ctx* ctx, const uint8_t* in, uint64_t in_size, 
                             const ndfl_member_item* items, ndfl_deflate_result* results, uint32_t n,
                             int dynamic, int min_run, int max_run, int min_dist, int max_dist,
                             uint32_t chunk_len, uint32_t hist_limit, uint32_t flags);
+
+/*
+ * ndfl_deflate_batch with a per-chunk choice of block: stream i is DeflaterOutputStream(out, chunk_len,
+ * hist_limit, MultiStrategy(strats...)): write all bytes, then finish() (D/comp/MultiStrategy.java:31-57,
+ * D/comp/Uncompressed.java:19-51).  Per chunk, the substrategy with the fewest bits at the current output bit
+ * position (mod 8) gives the block, the first such one on a tie; the stream starts at bit 0.  So a batch
+ * whose buffers want different block types -- a stored block for 64 random bytes, a fixed-code block for
+ * 512 bytes of text, a dynamic one for 4 KiB -- gets each of them, never pays for a dynamic header that does
+ * not pay back, and no stream is longer than under any one of its substrategies alone.  Still one kernel launch
+ * and one host sync whatever n and n_strats are (ndfl_deflate_chunks_multi costs one ndfl_deflate_chunks_lz77
+ * call per substrategy, an assemble kernel and several host waits per buffer).  Items, results, formats,
+ * `sum`, trailers, NDFL_E_CAPACITY with the required size, the rule that no byte of `out` outside
+ * [out_off, out_off + min(out_len, out_cap)) is written, flags, stream ordering, ndfl_ctx_last_kernel_ms,
+ * n == 0, overlapping or repeated input regions and the argument errors are ndfl_deflate_batch's, word for
+ * word.
+ *   strats      1..8 entries of NDFL_KIND_LZ77 (any tuple ndfl_deflate_chunks_lz77 accepts, the literal-only
+ *               form (0, 0, 0, 0) and the RLE form (3, 258, 1, 1) among them) or NDFL_KIND_UNCOMPRESSED.
+ *               n_strats == 0 or a null strats: NDFL_E_ARG; n_strats > 8: NDFL_E_UNSUPPORTED; another kind,
+ *               or invalid Lz77Huffman parameters: NDFL_E_ARG (all as ndfl_deflate_chunks_multi).  One
+ *               Lz77Huffman entry alone (or several equal ones) runs as ndfl_deflate_batch_lz77, one
+ *               Uncompressed entry alone gives the stored-only stream.
+ *   chunk_len   1..65536 (0: NDFL_E_ARG; above 65536: NDFL_E_UNSUPPORTED)
+ *   hist_limit  0..32768, else NDFL_E_ARG
+ * On any error nothing is written to `out` or `results`.
+ * A stream's DEFLATE bytes and end_bits are bit-identical to ndfl_deflate_chunks_multi(ctx, NULL, 0,
+ * hist_limit, data_i, len_i, chunk_len, strats, n_strats, 1, 0, ...).  A stored block is 3 header bits, zero
+ * bits up to the byte, LEN, NLEN and at most 65,535 bytes, so a 65,536-byte chunk is two of them; BFINAL is
+ * set on the stream's last block only; an empty buffer under Uncompressed alone is one empty stored block.
+ * The search's window, run and distance rules are ndfl_deflate_batch_lz77's, per substrategy.
+ * One wave encodes a stream.  It links a chunk's positions once, searches it once per distinct (min_run,
+ * max_run, min_dist, max_dist) among the substrategies (a static and a dynamic one with the same tuple share
+ * their tokens), sizes every candidate exactly from its histograms and codes, and keeps the best so far
+ * (tokens, codes, header) while it tries the rest.  Device memory the context owns: a link ring that holds a
+ * chunk and its window (at most 256 KiB) and two token lists (at most 256 KiB each) per wave, 768 KiB at
+ * most, sized from the batch's longest in_len, chunk_len and hist_limit, grown on first use, and never more
+ * than 256 MiB (the grid is lowered to fit: never below 341 waves).
+ * Crossover to a loop of ndfl_deflate_chunks_multi calls (measured on one MI355X, MultiStrategy(Uncompressed,
+ * FULL_STATIC, FULL_DYNAMIC) with a CRC-32, DESIGN.md §4 "Batched MultiStrategy deflate"): the loop costs 0.8 to
+ * 1.2 ms per buffer up to 1 MiB, nearly all of it per-call cost; the batch costs about 0.1 ms per call, a wave
+ * about 0.08 ms per stream plus 0.13 ms per KiB while the stream is a few KiB, 0.6 ms per KiB once its window is
+ * full, and up to 1,792 waves run at once.  65,536 x 512 B take 6.0 to 7.5 ms in a batch and 53 to 65 s in a
+ * loop, 4,096 x 4 KiB 1.9 to 3.5 ms and 3.7 to 4.3 s; 256 x 1 MiB take 619 to 824 ms in a batch and 268 to
+ * 318 ms in a loop: the batch loses there.  So one buffer alone is faster here below about 6 KB (0.18 ms + 0.13 ms
+ * per KiB against 1.0 ms), and with the full-window rate ten are below about 16 KB each, a hundred below about
+ * 170 KB, 256 below about 430 KB (0.18 ms + 0.6 ms per KiB against n x 1.0 ms).  Against ndfl_deflate_batch_lz77's
+ * FULL_DYNAMIC on the same buffers the kernel takes 5 to 11 % longer, and 512-byte text buffers come out at 92 %
+ * of their size instead of 101 %.
+ */
+int ndfl_deflate_batch_multi(ndfl_ctx* ctx, const uint8_t* in, uint64_t in_size, uint8_t* out, uint64_t out_size,
+                             const ndfl_member_item* items, ndfl_deflate_result* results, uint32_t n,
+                             const ndfl_strategy_desc* strats, uint32_t n_strats,
+                             uint32_t chunk_len, uint32_t hist_limit, uint32_t flags);
 
 /*
  * Decompress the block-aligned bit range [start_bit, end_bit) of one raw DEFLATE stream: one GPU's

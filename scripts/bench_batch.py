@@ -28,7 +28,11 @@ of each buffer, on the same three shapes; the lines are "bench": "batch_deflate"
 (--mode deflate-lz | deflate-lz-loop): one ndfl_deflate_batch_lz77 call against one
 ndfl_deflate_chunks_lz77 call per buffer, FULL_DYNAMIC, everything else the same; the lines are "bench":
 "batch_deflate_lz".  The four modes may share one run (--mode deflate,deflate-lz: both batch kernels on
-the same buffers, their kernel times and compressed sizes side by side).
+the same buffers, their kernel times and compressed sizes side by side).  With the per-chunk choice of
+block (--mode deflate-multi | deflate-multi-loop): one ndfl_deflate_batch_multi call against one
+ndfl_deflate_chunks_multi call per buffer, MultiStrategy(Uncompressed, FULL_STATIC, FULL_DYNAMIC); the
+lines are "bench": "batch_deflate_multi" (--mode deflate-lz,deflate-multi: what sizing two more
+candidates costs, and what it saves, on the same buffers).
 """
 import argparse
 import ctypes
@@ -107,7 +111,9 @@ def deflate_modes(a, modes):
     --mode deflate-loop: one ndfl_deflate_chunks call per buffer with crc_inout, which also runs on a
     build without the batch entry point (NDFL_LIB_PATH): the baseline.  --mode deflate-lz and
     deflate-lz-loop: the same with ndfl_deflate_batch_lz77 and ndfl_deflate_chunks_lz77, FULL_DYNAMIC
-    (the loop again runs on a build without the batch entry point).  Input and output are
+    (the loop again runs on a build without the batch entry point).  --mode deflate-multi and
+    deflate-multi-loop: ndfl_deflate_batch_multi and ndfl_deflate_chunks_multi with
+    MultiStrategy(Uncompressed, FULL_STATIC, FULL_DYNAMIC), likewise.  Input and output are
     device-resident; every buffer and every output region starts 16-byte aligned, and a region holds
     ndfl_deflate_bound bytes, so the loop's encoder writes it in place.  The first pass decodes every
     region with ndfl_inflate_members (raw + CRC-32) and compares the bytes and the checksums."""
@@ -119,6 +125,9 @@ def deflate_modes(a, modes):
     flags = ndfl.IN_DEVICE | ndfl.OUT_DEVICE
     strategy = ndfl._lib.STRATEGIES["RLE_DYNAMIC"]
     full_dynamic = (1, 3, 258, 1, 32768)             # Lz77Huffman.FULL_DYNAMIC
+    D = ndfl._lib.StrategyDesc                       # MultiStrategy(Uncompressed, FULL_STATIC, FULL_DYNAMIC)
+    t3 = (D * 3)(D(ndfl._lib.KIND_UNCOMPRESSED, 0, 0, 0, 0, 0), D(ndfl._lib.KIND_LZ77, 0, 3, 258, 1, 32768),
+                 D(ndfl._lib.KIND_LZ77, 1, 3, 258, 1, 32768))
     chunk_len, hist_limit = 65536, 32768
     u64, u32 = ctypes.c_uint64, ctypes.c_uint32
     for name in a.shapes.split(","):
@@ -137,7 +146,8 @@ def deflate_modes(a, modes):
         pi, po = d_in.data_ptr(), d_out.data_ptr()
         for mode in modes:
             out_lens, sums = [0] * n, [0] * n
-            batch, lz = mode in ("deflate", "deflate-lz"), mode in ("deflate-lz", "deflate-lz-loop")
+            batch, lz = mode in ("deflate", "deflate-lz", "deflate-multi"), mode in ("deflate-lz", "deflate-lz-loop")
+            multi = mode in ("deflate-multi", "deflate-multi-loop")
             if batch:
                 arr = (ndfl._lib.MemberItem * n)(*[ndfl._lib.MemberItem(i * in_stride, size, i * cap, cap, ndfl._lib.FMT_RAW,
                                                                         ndfl._lib.SUM_CRC32) for i in range(n)])
@@ -145,7 +155,10 @@ def deflate_modes(a, modes):
 
             def once():
                 if batch:
-                    if lz:
+                    if multi:
+                        rc = L.ndfl_deflate_batch_multi(ctx._h, pi, n * in_stride, po, n * cap, arr, res, n, t3, 3, chunk_len,
+                                                        hist_limit, flags)
+                    elif lz:
                         rc = L.ndfl_deflate_batch_lz77(ctx._h, pi, n * in_stride, po, n * cap, arr, res, n, *full_dynamic,
                                                        chunk_len, hist_limit, flags)
                     else:
@@ -156,7 +169,11 @@ def deflate_modes(a, modes):
                 bits, crc = u64(0), u32(0)
                 for i in range(n):
                     crc.value = 0
-                    if lz:
+                    if multi:
+                        rc = L.ndfl_deflate_chunks_multi(ctx._h, None, 0, hist_limit, pi + i * in_stride, size, chunk_len, t3,
+                                                         3, 1, 0, po + i * cap, cap, ctypes.byref(bits), ctypes.byref(crc),
+                                                         flags)
+                    elif lz:
                         rc = L.ndfl_deflate_chunks_lz77(ctx._h, None, 0, hist_limit, pi + i * in_stride, size, chunk_len,
                                                         *full_dynamic, 1, 0, po + i * cap, cap, ctypes.byref(bits),
                                                         ctypes.byref(crc), flags)
@@ -189,9 +206,9 @@ def deflate_modes(a, modes):
                 if it >= a.warmup:
                     times.append(dt)
             med = statistics.median(times)
-            line = {"bench": "batch_deflate_lz" if lz else "batch_deflate", "label": a.label, "mode": mode, "data": a.data,
+            line = {"bench": "batch_deflate_multi" if multi else "batch_deflate_lz" if lz else "batch_deflate", "label": a.label, "mode": mode, "data": a.data,
                     "shape": name, "buffers": n, "buffer_bytes": size, "in_bytes": n * size, "out_bytes": sum(out_lens),
-                    "strategy": "FULL_DYNAMIC" if lz else "RLE_DYNAMIC",
+                    "strategy": "MULTI(UNCOMPRESSED,FULL_STATIC,FULL_DYNAMIC)" if multi else "FULL_DYNAMIC" if lz else "RLE_DYNAMIC",
                     "ms_median": round(med, 3), "ms_all": [round(t, 3) for t in times],
                     "in_MBps": round(n * size / med / 1e3, 1)}
             if kms is not None:
@@ -204,7 +221,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", required=True,
                     help="comma-separated: loop, batch, members, batch+sum; or deflate, deflate-loop, deflate-lz, "
-                         "deflate-lz-loop")
+                         "deflate-lz-loop, deflate-multi, deflate-multi-loop")
     ap.add_argument("--data", choices=["text", "runs"], default="text", help="deflate modes: the buffers' content")
     ap.add_argument("--format", choices=["zlib", "gzip", "raw-crc"], default="zlib",
                     help="members / batch+sum: the container of each stream")
@@ -214,7 +231,8 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--label", default="")
     a = ap.parse_args()
-    if all(m in ("deflate", "deflate-loop", "deflate-lz", "deflate-lz-loop") for m in a.mode.split(",")):
+    if all(m in ("deflate", "deflate-loop", "deflate-lz", "deflate-lz-loop", "deflate-multi", "deflate-multi-loop")
+           for m in a.mode.split(",")):
         return deflate_modes(a, a.mode.split(","))
     import torch
     import ndfl
