@@ -10,6 +10,7 @@
 #include "../hip/deflate_batch.hip"
 #include "../hip/deflate_batch_lz.hip"
 #include "../hip/deflate_batch_multi.hip"
+#include "../hip/deflate_batch_binsplit.hip"
 
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -481,6 +482,27 @@ int ndfl_deflate_batch_multi(ndfl_ctx* c, const uint8_t* in, uint64_t in_size, u
     if (const int e = deflate_batch_args(in, in_size, out, out_size, items, results, n, chunk_len, hist_limit)) return e;
     HIPCHK(hipSetDevice(c->device));
     launch.a.n = n; launch.a.chunk_len = chunk_len; launch.a.hist_limit = hist_limit;
+    launch.a.crc_tab = c->d_tabs.as<uint32_t>();
+    return batch_status(deflate_batch_run(c->batch, &c->d_in.p, &c->d_in.cap, ordered_stream(c), c->ev0, c->ev1, in, out,
+                                          items, results, n, flags, launch, &c->last_ms));
+}
+
+int ndfl_deflate_batch_binsplit(ndfl_ctx* c, const uint8_t* in, uint64_t in_size, uint8_t* out, uint64_t out_size,
+                                const ndfl_member_item* items, ndfl_deflate_result* results, uint32_t n,
+                                const ndfl_strategy_desc* sub, int32_t min_block_len, uint32_t chunk_len,
+                                uint32_t hist_limit, uint32_t flags) {
+    if (!c) return NDFL_E_ARG;
+    if (n == 0) return NDFL_OK;
+    if (!sub || min_block_len < 1) return NDFL_E_ARG;                                           // (D/comp/BinarySplit.java:23-24)
+    // as ndfl_deflate_chunks_binsplit: the frame's checks, then the substrategy
+    if (const int e = deflate_batch_args(in, in_size, out, out_size, items, results, n, chunk_len, hist_limit)) return e;
+    if (sub->kind != NDFL_KIND_LZ77) return NDFL_E_UNSUPPORTED;     // position-independent substrategies only
+    if (!lz77_tuple_valid(desc_tuple(*sub))) return NDFL_E_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    BatchBinsplitLaunch launch{c->batch_lz, c->knobs, items, dbsp::Args{}};
+    launch.set_search(*sub);
+    launch.a.n = n; launch.a.chunk_len = chunk_len; launch.a.hist_limit = hist_limit;
+    launch.a.min_block = (uint32_t)min_block_len;
     launch.a.crc_tab = c->d_tabs.as<uint32_t>();
     return batch_status(deflate_batch_run(c->batch, &c->d_in.p, &c->d_in.cap, ordered_stream(c), c->ev0, c->ev1, in, out,
                                           items, results, n, flags, launch, &c->last_ms));

@@ -276,6 +276,23 @@ __device__ __forceinline__ void emit_tokens(Lds& S, BitOut& bo, const uint32_t* 
     }
 }
 
+// For the callers that size a block before they emit it (deflate_batch_multi.hip, deflate_batch_binsplit.hip).
+// The bits of the block's tokens and its end-of-block code under the codes in S.litCode / S.distCode,
+// from the histograms (hdist0: the distances before the builder's dummy neighbour).
+__device__ __forceinline__ uint32_t token_bits(Lds& S) {
+    const int lane = opaque_lane();
+    uint32_t b = 0;
+    for (uint32_t t = (uint32_t)lane; t < 288; t += 64) {
+        const uint32_t ex = (t < 265 || t >= 285) ? 0u : (t - 261) >> 2;      // extra bits of a length symbol
+        b += S.scr.hlit[t] * ((S.litCode[t] >> 16) + ex);
+    }
+    if (lane < 30) {
+        const uint32_t ex = lane < 4 ? 0u : ((uint32_t)lane - 2) >> 1;        // of a distance symbol
+        b += S.scr.hdist0[lane] * ((S.distCode[lane] >> 16) + ex);
+    }
+    return rfl(dbat::wave_sum_l(b, lane));
+}
+
 }  // namespace dblz
 
 extern "C" __global__ void __launch_bounds__(64)

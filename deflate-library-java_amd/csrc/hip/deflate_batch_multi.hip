@@ -83,21 +83,7 @@ struct Lds : dblz::Lds {
     uint32_t b_hdr[HDRW];     // and its header words
 };
 
-// The bits of the block's tokens and its end-of-block code under the codes in S.litCode / S.distCode,
-// from the histograms (hdist0: the distances before the builder's dummy neighbour).
-__device__ __forceinline__ uint32_t token_bits(Lds& S) {
-    const int lane = opaque_lane();
-    uint32_t b = 0;
-    for (uint32_t t = (uint32_t)lane; t < 288; t += 64) {
-        const uint32_t ex = (t < 265 || t >= 285) ? 0u : (t - 261) >> 2;      // extra bits of a length symbol
-        b += S.scr.hlit[t] * ((S.litCode[t] >> 16) + ex);
-    }
-    if (lane < 30) {
-        const uint32_t ex = lane < 4 ? 0u : ((uint32_t)lane - 2) >> 1;        // of a distance symbol
-        b += S.scr.hdist0[lane] * ((S.distCode[lane] >> 16) + ex);
-    }
-    return rfl(dbat::wave_sum_l(b, lane));
-}
+using dblz::token_bits;       // a block's exact size from its histograms (shared with deflate_batch_binsplit.hip)
 
 // The chunk's len_c bytes at cp as stored blocks (D/comp/Uncompressed.java:32-46).  The walk's own
 // values are parked across make_room (v_cp, v_len_c, v_final: parked by the caller).

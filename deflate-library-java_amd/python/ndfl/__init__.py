@@ -166,8 +166,9 @@ class MultiStrategy:
 class BinarySplit:
     """BinarySplit(strat, minBlockLen) (D/comp/BinarySplit.java:15-82): halve each chunk recursively
     while both halves exceed minBlockLen, keeping a split when it takes fewer bits.  Over an
-    Lz77Huffman the whole stream is batched on the GPU (ndfl_deflate_chunks_binsplit); over any
-    other Strategy it runs per chunk (ndfl.plugin: ndfl_decide for the library's classes)."""
+    Lz77Huffman the whole stream is batched on the GPU (ndfl_deflate_chunks_binsplit; many buffers in
+    one launch: Context.deflate_batch, ndfl_deflate_batch_binsplit); over any other Strategy it runs per
+    chunk (ndfl.plugin: ndfl_decide for the library's classes)."""
 
     def __init__(self, strat, minBlockLen):
         if strat is None:
@@ -469,6 +470,16 @@ class Context:
                                in_addr, in_size, out_addr, out_size, items, arr, len(descs), chunk_len, hist_limit,
                                flags)
 
+    def deflate_batch_binsplit_raw(self, in_addr, in_size, out_addr, out_size, items, sub, min_block_len, chunk_len,
+                                   hist_limit, flags):
+        """ndfl_deflate_batch_binsplit: deflate_batch_raw with BinarySplit(sub, min_block_len) as the strategy,
+        `sub` an Lz77Huffman (or a ready-made _lib.StrategyDesc record, or None for a null pointer); the
+        same items and the same (status, checksum, out_len, end_bits) per stream."""
+        d = sub if sub is None or isinstance(sub, _lib.StrategyDesc) else _desc(sub)
+        return self._batch_raw("ndfl_deflate_batch_binsplit", _lib.MemberItem, _lib.DeflateResult, self._DEFLATE_RESULT,
+                               in_addr, in_size, out_addr, out_size, items, None if d is None else ctypes.byref(d),
+                               min_block_len, chunk_len, hist_limit, flags)
+
     @staticmethod
     def _batch_subs(strategy):
         """The substrategies ndfl_deflate_batch_multi takes for `strategy` (Uncompressed.SINGLETON, or a
@@ -490,11 +501,16 @@ class Context:
         L = load()
         buffers = [bytes(b) for b in buffers]
         subs = self._batch_subs(strategy)
+        split = isinstance(strategy, BinarySplit)
+        if split and not isinstance(strategy.substrategy, Lz77Huffman):
+            raise NdflError(_lib.E_UNSUPPORTED, "ndfl_deflate_batch_binsplit")
         packed = b"".join(buffers)
         src = ctypes.create_string_buffer(packed, max(1, len(packed)))
         items, regions, in_off, out_off = [], [], 0, 0
         for b, h in zip(buffers, headers):
-            cap = L.ndfl_deflate_bound(len(b), chunk_len) * (2 if isinstance(strategy, Lz77Huffman) or subs else 1) + 8
+            # (BinarySplit: its Lz77Huffman's size, a split is taken only when it is shorter)
+            cap = L.ndfl_deflate_bound(len(b), chunk_len) * (2 if isinstance(strategy, Lz77Huffman) or subs or split
+                                                             else 1) + 8
             if subs:
                 # the larger of that and the stored size (5 bytes a block, two blocks for a 65,536-byte
                 # chunk), and a byte per chunk for the bits the choice depends on the bit position by
@@ -510,6 +526,10 @@ class Context:
         if subs:
             res = self.deflate_batch_multi_raw(ctypes.addressof(src), len(packed), ctypes.addressof(out), out_off, items,
                                                subs, chunk_len, hist_limit, 0)
+        elif split:
+            res = self.deflate_batch_binsplit_raw(ctypes.addressof(src), len(packed), ctypes.addressof(out), out_off, items,
+                                                  strategy.substrategy, strategy.minimumBlockLength, chunk_len, hist_limit,
+                                                  0)
         elif isinstance(strategy, Lz77Huffman):      # (a preset's name or id keeps ndfl_deflate_batch)
             res = self.deflate_batch_lz77_raw(ctypes.addressof(src), len(packed), ctypes.addressof(out), out_off, items,
                                               strategy.useDynamicHuffmanCodes, *strategy.params, chunk_len, hist_limit, 0)
@@ -527,8 +547,9 @@ class Context:
         """Compress many independent host buffers in one call, each as deflate() compresses it alone
         (RLE_* / LITERAL_* presets by name or id through ndfl_deflate_batch; an Lz77Huffman instance, FULL_*
         among them, through ndfl_deflate_batch_lz77; Uncompressed.SINGLETON, or a MultiStrategy over a flat
-        list of at most 8 Lz77Huffman / Uncompressed, through ndfl_deflate_batch_multi; any other
-        MultiStrategy raises NdflError(E_UNSUPPORTED)).  Returns one (bytes, end_bits, checksum) per buffer; checksum is
+        list of at most 8 Lz77Huffman / Uncompressed, through ndfl_deflate_batch_multi; a BinarySplit over an
+        Lz77Huffman through ndfl_deflate_batch_binsplit; any other MultiStrategy or BinarySplit raises
+        NdflError(E_UNSUPPORTED)).  Returns one (bytes, end_bits, checksum) per buffer; checksum is
         the buffer's CRC-32 / Adler-32 with sum = SUM_CRC32 / SUM_ADLER32, else 0."""
         buffers = list(buffers)
         kind = _lib.SUM_NONE if sum is None else int(sum)
@@ -539,7 +560,8 @@ class Context:
         """Compress many independent host buffers into complete zlib (FMT_ZLIB) or gzip (FMT_GZIP)
         members in one call: what ZlibOutputStream / GzipOutputStream write for each buffer alone.  The
         header is `meta`'s (a ZlibMetadata / GzipMetadata; default ZlibMetadata.DEFAULT / GzipMetadata()),
-        the trailer the kernel's; `strategy` as for deflate_batch.  Returns one bytes object per buffer."""
+        the trailer the kernel's; `strategy` as for deflate_batch (BinarySplit(Lz77Huffman, minBlockLen) through
+        ndfl_deflate_batch_binsplit among them).  Returns one bytes object per buffer."""
         from .streams import GzipMetadata, ZlibMetadata
         buffers = list(buffers)
         fmt = int(format)

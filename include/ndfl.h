@@ -498,6 +498,71 @@ int ndfl_deflate_batch_multi(ndfl_ctx* ctx, const uint8_t* in, uint64_t in_size,
                              uint32_t chunk_len, uint32_t hist_limit, uint32_t flags);
 
 /*
+ * ndfl_deflate_batch with split blocks: stream i is DeflaterOutputStream(out, chunk_len, hist_limit,
+ * BinarySplit(Lz77Huffman(sub's dynamic, min_run, max_run, min_dist, max_dist), min_block_len)): write all
+ * bytes, then finish() (D/comp/BinarySplit.java:21-82).  A record with mixed content -- header then body,
+ * digits then text, text then binary -- gets a block and a code of its own for each part where that is
+ * shorter, and no stream is longer than under `sub` alone.  Still one kernel launch and one host sync whatever
+ * n is (ndfl_deflate_chunks_binsplit costs one sub-frame per halving level, a host recursion and an assemble
+ * kernel per buffer).  Items, results, formats, `sum`, trailers, NDFL_E_CAPACITY with the required size, the
+ * rule that no byte of `out` outside [out_off, out_off + min(out_len, out_cap)) is written, flags, stream
+ * ordering, ndfl_ctx_last_kernel_ms, n == 0, overlapping or repeated input regions and the chunk_len and
+ * hist_limit checks are ndfl_deflate_batch's, word for word.
+ *   sub, min_block_len
+ *               checked in ndfl_deflate_chunks_binsplit's order: a null sub or min_block_len < 1 is NDFL_E_ARG
+ *               (D/comp/BinarySplit.java:23-24); then chunk_len, hist_limit, the pointers and the items as
+ *               ndfl_deflate_batch; then sub->kind other than NDFL_KIND_LZ77 is NDFL_E_UNSUPPORTED (Uncompressed
+ *               and MultiStrategy size a block by the bit position it starts at, which no fixed tree answers);
+ *               then an invalid Lz77Huffman tuple is NDFL_E_ARG.  The literal-only form (0, 0, 0, 0) and the
+ *               RLE form (3, 258, 1, 1) are valid tuples.
+ *   chunk_len   1..65536 (0: NDFL_E_ARG; above 65536: NDFL_E_UNSUPPORTED)
+ *   hist_limit  0..32768, else NDFL_E_ARG
+ * On any error nothing is written to `out` or `results`.
+ * The decision rule.  Lz77Huffman's bit lengths do not depend on the bit position, so the reference's recursion
+ * (D/comp/BinarySplit.java:36-69) is: a block [a, a + n) of a chunk has the halves f = (n + 1) / 2 and
+ * s = n - f; it is split iff min(f, s) > min_block_len and bits(a, f) + bits(a + f, s) < bits(a, n), where
+ * bits() is the size of the range as one Lz77Huffman block; each half is then treated the same way.  A
+ * sub-block's window starts where its chunk's does (:44-46): at position q of a chunk that starts at stream
+ * offset cs the candidates are the distances min_dist .. min(max_dist, q - (cs - min(hist_limit, cs))), and a
+ * run is capped at the sub-block's end.  BFINAL is set on the stream's last block only; an empty buffer gives
+ * the one empty final block.  dynamic == 0 runs the same rule: two fresh greedy parses can be shorter than one.
+ * Unlike ndfl_deflate_chunks_binsplit the call has no restriction on odd lengths or on the number of nodes: any
+ * in_len, any chunk_len in 1..65536 and any min_block_len >= 1 is encoded.  Where that call accepts the input
+ * (ctx, NULL, 0, hist_limit, data_i, len_i, chunk_len, sub, min_block_len, 1, 0, ...) the DEFLATE bytes and
+ * end_bits are bit-identical.
+ * One wave encodes a stream.  It links a chunk's positions once and walks the split tree depth-first, the left
+ * half first, with the waiting right halves on a stack in LDS (at most 15): every node is searched and sized
+ * once, exactly, from its histograms and codes, and a leaf is emitted as soon as it is known to be one --
+ * without another search when its tokens and codes are still the ones in place, as for a chunk too short to
+ * split, which costs the one search of ndfl_deflate_batch_lz77.  Device memory the context owns: a link ring that
+ * holds a chunk and its window (at most 256 KiB) and one token list (at most 256 KiB) per wave, sized from the
+ * batch's longest in_len, chunk_len and hist_limit, grown on first use, and never more than 256 MiB (the grid is
+ * lowered to fit: never below 512 waves).
+ * Cost: a chunk is searched once per level of the tree that is tried, plus once more for the leaves that are
+ * built again: up to log2(chunk_len / min_block_len) + 2 searches of the chunk's bytes.
+ * Crossover to a loop of ndfl_deflate_chunks_binsplit calls (measured on one MI355X, BinarySplit(FULL_DYNAMIC, 256)
+ * with a CRC-32, chunk_len = min(the buffer, 65536), DESIGN.md §4 "Batched BinarySplit deflate"; "mixed" buffers
+ * are a quarter each of digits, text, random bytes and 16-valued bytes, which split, "text" ones never do): the
+ * loop costs 0.56 ms per 512-byte buffer (no level to try), 1.9 to 2.1 ms per 4 KiB buffer (three levels), 4.8 to
+ * 6.8 ms per 1 MiB buffer; the batch costs about 0.1 ms per call, a wave 0.15 ms per 512-byte stream, 1.6 (text)
+ * to 2.6 ms (mixed) per 4 KiB stream, and 1.8 to 2.3 ms per KiB of a 1 MiB stream, seven levels tried with the
+ * window full; up to 1,792 waves run at once.  65,536 x 512 B take 5.7 to 6.0 ms in a batch and 37 s in a loop
+ * (2,048 of them measured: 1.15 to 1.17 s), 4,096 x 4 KiB 4.9 to 8.0 ms and 7.6 to 8.7 s; 256 x 1 MiB take 1.81
+ * to 2.36 s in a batch and 1.22 to 1.74 s in a loop: the batch loses there, as the LZ77 and MultiStrategy batches
+ * do.  So one buffer alone is faster here below about 4 KB (at 4 KiB: 1.7 to 2.7 ms against 1.9 to 2.1 ms), and
+ * with the full-window rate, which overstates the batch below some tens of KiB, ten are below about 10 KB each, a
+ * hundred below about 115 KB, 256 below about 470 KB (0.1 ms + 2.3 ms per KiB against n x (2.1 ms + 0.0046 ms per
+ * KiB)).  Against ndfl_deflate_batch_lz77's
+ * FULL_DYNAMIC on the same buffers the kernel takes 4 % longer on 512-byte buffers, which are too short to split
+ * (one search per stream), 2.9 (text) to 4.9 (mixed) times as long on 4 KiB buffers and 3.2 times on 1 MiB ones;
+ * mixed 4 KiB buffers come out at 72.3 % of their size instead of 77.8 %, text ones gain nothing.
+ */
+int ndfl_deflate_batch_binsplit(ndfl_ctx* ctx, const uint8_t* in, uint64_t in_size, uint8_t* out, uint64_t out_size,
+                                const ndfl_member_item* items, ndfl_deflate_result* results, uint32_t n,
+                                const ndfl_strategy_desc* sub, int32_t min_block_len,
+                                uint32_t chunk_len, uint32_t hist_limit, uint32_t flags);
+
+/*
  * Decompress the block-aligned bit range [start_bit, end_bit) of one raw DEFLATE stream: one GPU's
  * shard of a stream decoded across GPUs, or one batch of a stream read incrementally
  * (NDFL_IN_PARTIAL, end_bit UINT64_MAX: InflaterInputStream's bounded input buffer,

@@ -32,7 +32,14 @@ the same buffers, their kernel times and compressed sizes side by side).  With t
 block (--mode deflate-multi | deflate-multi-loop): one ndfl_deflate_batch_multi call against one
 ndfl_deflate_chunks_multi call per buffer, MultiStrategy(Uncompressed, FULL_STATIC, FULL_DYNAMIC); the
 lines are "bench": "batch_deflate_multi" (--mode deflate-lz,deflate-multi: what sizing two more
-candidates costs, and what it saves, on the same buffers).
+candidates costs, and what it saves, on the same buffers).  With split blocks (--mode deflate-binsplit |
+deflate-binsplit-loop): one ndfl_deflate_batch_binsplit call against one ndfl_deflate_chunks_binsplit call
+per buffer, BinarySplit(FULL_DYNAMIC, 256); the lines are "bench": "batch_deflate_binsplit".  The loop's
+call refuses halvings of an odd length, so the comparison needs buffer sizes that are powers of two with
+chunk_len equal to the buffer size (65,536 for the 1 MiB shape: 16 full chunks); these two modes, and
+deflate-lz next to them in one run, use that chunk_len.  512-byte buffers are too short to split at 256
+(one search per stream); --data mixed (a quarter each of digits, the text, random bytes and 16-valued
+bytes) gives the larger ones something to split.
 """
 import argparse
 import ctypes
@@ -101,6 +108,11 @@ def make_buffers(name, seed, kind):
             which = np.repeat(np.arange(2 * m), seg)[:size]
             text = np.frombuffer(data, dtype=np.uint8)
             data = np.where(which & 1, vals[which >> 1], text).astype(np.uint8).tobytes()
+        if kind == "mixed":
+            q = size // 4
+            text = np.frombuffer(data, dtype=np.uint8)
+            data = np.concatenate([text[:q] % 10 + 48, text[q:2 * q], rs.randint(0, 256, q).astype(np.uint8),
+                                   text[3 * q:] % 16 + 192]).astype(np.uint8).tobytes()
         assert len(data) == size
         datas.append(data)
     return datas
@@ -113,7 +125,10 @@ def deflate_modes(a, modes):
     deflate-lz-loop: the same with ndfl_deflate_batch_lz77 and ndfl_deflate_chunks_lz77, FULL_DYNAMIC
     (the loop again runs on a build without the batch entry point).  --mode deflate-multi and
     deflate-multi-loop: ndfl_deflate_batch_multi and ndfl_deflate_chunks_multi with
-    MultiStrategy(Uncompressed, FULL_STATIC, FULL_DYNAMIC), likewise.  Input and output are
+    MultiStrategy(Uncompressed, FULL_STATIC, FULL_DYNAMIC), likewise.  --mode deflate-binsplit and
+    deflate-binsplit-loop: ndfl_deflate_batch_binsplit and ndfl_deflate_chunks_binsplit with
+    BinarySplit(FULL_DYNAMIC, 256), likewise, with chunk_len = min(the buffer size, 65536) for every mode of
+    the run (the loop refuses halvings of an odd length).  Input and output are
     device-resident; every buffer and every output region starts 16-byte aligned, and a region holds
     ndfl_deflate_bound bytes, so the loop's encoder writes it in place.  The first pass decodes every
     region with ndfl_inflate_members (raw + CRC-32) and compares the bytes and the checksums."""
@@ -128,11 +143,17 @@ def deflate_modes(a, modes):
     D = ndfl._lib.StrategyDesc                       # MultiStrategy(Uncompressed, FULL_STATIC, FULL_DYNAMIC)
     t3 = (D * 3)(D(ndfl._lib.KIND_UNCOMPRESSED, 0, 0, 0, 0, 0), D(ndfl._lib.KIND_LZ77, 0, 3, 258, 1, 32768),
                  D(ndfl._lib.KIND_LZ77, 1, 3, 258, 1, 32768))
-    chunk_len, hist_limit = 65536, 32768
+    fd = D(ndfl._lib.KIND_LZ77, 1, 3, 258, 1, 32768)  # BinarySplit(FULL_DYNAMIC, 256)
+    min_block_len = 256
+    hist_limit = 32768
     u64, u32 = ctypes.c_uint64, ctypes.c_uint32
     for name in a.shapes.split(","):
         n, size = SHAPES[name]
+        chunk_len = min(size, 65536) if any("binsplit" in m for m in modes) else 65536
         datas = make_buffers(name, a.seed, a.data)
+        if a.buffers:
+            n = min(n, a.buffers)
+            datas = datas[:n]
         want = b"".join(datas)
         crcs = [zlib.crc32(d) for d in datas]
         in_stride = (size + 15) // 16 * 16
@@ -146,8 +167,10 @@ def deflate_modes(a, modes):
         pi, po = d_in.data_ptr(), d_out.data_ptr()
         for mode in modes:
             out_lens, sums = [0] * n, [0] * n
-            batch, lz = mode in ("deflate", "deflate-lz", "deflate-multi"), mode in ("deflate-lz", "deflate-lz-loop")
+            batch = mode in ("deflate", "deflate-lz", "deflate-multi", "deflate-binsplit")
+            lz = mode in ("deflate-lz", "deflate-lz-loop")
             multi = mode in ("deflate-multi", "deflate-multi-loop")
+            split = mode in ("deflate-binsplit", "deflate-binsplit-loop")
             if batch:
                 arr = (ndfl._lib.MemberItem * n)(*[ndfl._lib.MemberItem(i * in_stride, size, i * cap, cap, ndfl._lib.FMT_RAW,
                                                                         ndfl._lib.SUM_CRC32) for i in range(n)])
@@ -155,7 +178,10 @@ def deflate_modes(a, modes):
 
             def once():
                 if batch:
-                    if multi:
+                    if split:
+                        rc = L.ndfl_deflate_batch_binsplit(ctx._h, pi, n * in_stride, po, n * cap, arr, res, n, ctypes.byref(fd),
+                                                           min_block_len, chunk_len, hist_limit, flags)
+                    elif multi:
                         rc = L.ndfl_deflate_batch_multi(ctx._h, pi, n * in_stride, po, n * cap, arr, res, n, t3, 3, chunk_len,
                                                         hist_limit, flags)
                     elif lz:
@@ -169,7 +195,11 @@ def deflate_modes(a, modes):
                 bits, crc = u64(0), u32(0)
                 for i in range(n):
                     crc.value = 0
-                    if multi:
+                    if split:
+                        rc = L.ndfl_deflate_chunks_binsplit(ctx._h, None, 0, hist_limit, pi + i * in_stride, size, chunk_len,
+                                                            ctypes.byref(fd), min_block_len, 1, 0, po + i * cap, cap,
+                                                            ctypes.byref(bits), ctypes.byref(crc), flags)
+                    elif multi:
                         rc = L.ndfl_deflate_chunks_multi(ctx._h, None, 0, hist_limit, pi + i * in_stride, size, chunk_len, t3,
                                                          3, 1, 0, po + i * cap, cap, ctypes.byref(bits), ctypes.byref(crc),
                                                          flags)
@@ -206,9 +236,11 @@ def deflate_modes(a, modes):
                 if it >= a.warmup:
                     times.append(dt)
             med = statistics.median(times)
-            line = {"bench": "batch_deflate_multi" if multi else "batch_deflate_lz" if lz else "batch_deflate", "label": a.label, "mode": mode, "data": a.data,
+            line = {"bench": "batch_deflate_binsplit" if split else "batch_deflate_multi" if multi else "batch_deflate_lz" if lz
+                    else "batch_deflate", "label": a.label, "mode": mode, "data": a.data,
                     "shape": name, "buffers": n, "buffer_bytes": size, "in_bytes": n * size, "out_bytes": sum(out_lens),
-                    "strategy": "MULTI(UNCOMPRESSED,FULL_STATIC,FULL_DYNAMIC)" if multi else "FULL_DYNAMIC" if lz else "RLE_DYNAMIC",
+                    "strategy": "BINSPLIT(FULL_DYNAMIC,256)" if split else "MULTI(UNCOMPRESSED,FULL_STATIC,FULL_DYNAMIC)" if multi
+                    else "FULL_DYNAMIC" if lz else "RLE_DYNAMIC", "chunk_len": chunk_len,
                     "ms_median": round(med, 3), "ms_all": [round(t, 3) for t in times],
                     "in_MBps": round(n * size / med / 1e3, 1)}
             if kms is not None:
@@ -221,8 +253,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", required=True,
                     help="comma-separated: loop, batch, members, batch+sum; or deflate, deflate-loop, deflate-lz, "
-                         "deflate-lz-loop, deflate-multi, deflate-multi-loop")
-    ap.add_argument("--data", choices=["text", "runs"], default="text", help="deflate modes: the buffers' content")
+                         "deflate-lz-loop, deflate-multi, deflate-multi-loop, deflate-binsplit, deflate-binsplit-loop")
+    ap.add_argument("--data", choices=["text", "runs", "mixed"], default="text", help="deflate modes: the buffers' content")
+    ap.add_argument("--buffers", type=int, default=0, help="deflate modes: only the first N buffers of each shape")
     ap.add_argument("--format", choices=["zlib", "gzip", "raw-crc"], default="zlib",
                     help="members / batch+sum: the container of each stream")
     ap.add_argument("--shapes", default=",".join(SHAPES))
@@ -231,8 +264,8 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--label", default="")
     a = ap.parse_args()
-    if all(m in ("deflate", "deflate-loop", "deflate-lz", "deflate-lz-loop", "deflate-multi", "deflate-multi-loop")
-           for m in a.mode.split(",")):
+    if all(m in ("deflate", "deflate-loop", "deflate-lz", "deflate-lz-loop", "deflate-multi", "deflate-multi-loop",
+                 "deflate-binsplit", "deflate-binsplit-loop") for m in a.mode.split(",")):
         return deflate_modes(a, a.mode.split(","))
     import torch
     import ndfl
