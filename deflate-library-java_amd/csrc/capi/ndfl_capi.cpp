@@ -372,7 +372,7 @@ static bool member_items_valid(const ndfl_member_item* items, uint32_t n) {
     return true;
 }
 
-// What the two batched deflate calls check after their strategy, in this order: chunk_len and
+// What the batched deflate calls check of their frame, in this order: chunk_len and
 // hist_limit, the call-level rules, the items.
 static int deflate_batch_args(const uint8_t* in, uint64_t in_size, const uint8_t* out, uint64_t out_size,
                               const ndfl_member_item* items, const void* results, uint32_t n, uint32_t chunk_len,
@@ -386,6 +386,17 @@ static int deflate_batch_args(const uint8_t* in, uint64_t in_size, const uint8_t
 
 // A batch runner's return code as the C ABI's.
 static int batch_status(int r) { return !r ? NDFL_OK : r == -4 ? NDFL_E_DEVICE : NDFL_E_INTERNAL; }
+
+// How the four batched deflate calls end once their arguments are checked: the frame's arguments and the
+// checksum tables into the launcher, which holds what is the call's own already, and the run.
+template <class Launch>
+static int deflate_batch_launch(ndfl_ctx* c, Launch& launch, const uint8_t* in, uint8_t* out, const ndfl_member_item* items,
+                                ndfl_deflate_result* results, uint32_t n, uint32_t chunk_len, uint32_t flags) {
+    HIPCHK(hipSetDevice(c->device));
+    launch.a.n = n; launch.a.chunk_len = chunk_len; launch.a.crc_tab = c->d_tabs.as<uint32_t>();
+    return batch_status(deflate_batch_run(c->batch, &c->d_in.p, &c->d_in.cap, ordered_stream(c), c->ev0, c->ev1, in, out,
+                                          items, results, n, flags, launch, &c->last_ms));
+}
 
 extern "C" {
 
@@ -430,11 +441,8 @@ int ndfl_deflate_batch(ndfl_ctx* c, const uint8_t* in, uint64_t in_size, uint8_t
         default: return NDFL_E_ARG;
     }
     if (const int e = deflate_batch_args(in, in_size, out, out_size, items, results, n, chunk_len, hist_limit)) return e;
-    HIPCHK(hipSetDevice(c->device));
-    launch.a.n = n; launch.a.chunk_len = chunk_len; launch.a.hist_enabled = hist_limit > 0;
-    launch.a.crc_tab = c->d_tabs.as<uint32_t>(); launch.a.crc_x = launch.a.crc_tab + 1024;
-    return batch_status(deflate_batch_run(c->batch, &c->d_in.p, &c->d_in.cap, ordered_stream(c), c->ev0, c->ev1, in, out,
-                                          items, results, n, flags, launch, &c->last_ms));
+    launch.a.hist_enabled = hist_limit > 0; launch.a.crc_x = c->d_tabs.as<uint32_t>() + 1024;
+    return deflate_batch_launch(c, launch, in, out, items, results, n, chunk_len, flags);
 }
 
 int ndfl_deflate_batch_lz77(ndfl_ctx* c, const uint8_t* in, uint64_t in_size, uint8_t* out, uint64_t out_size,
@@ -450,14 +458,11 @@ int ndfl_deflate_batch_lz77(ndfl_ctx* c, const uint8_t* in, uint64_t in_size, ui
     if (preset >= 0)
         return ndfl_deflate_batch(c, in, in_size, out, out_size, items, results, n, preset, chunk_len, hist_limit, flags);
     if (const int e = deflate_batch_args(in, in_size, out, out_size, items, results, n, chunk_len, hist_limit)) return e;
-    HIPCHK(hipSetDevice(c->device));
     BatchLzLaunch launch{c->batch_lz, c->knobs, items, dblz::Args{}};
-    launch.a.n = n; launch.a.chunk_len = chunk_len; launch.a.hist_limit = hist_limit; launch.a.dynamic = dynamic != 0;
+    launch.a.hist_limit = hist_limit; launch.a.dynamic = dynamic != 0;
     launch.a.min_run = (uint32_t)min_run; launch.a.max_run = (uint32_t)max_run;
     launch.a.min_dist = (uint32_t)min_dist; launch.a.max_dist = (uint32_t)max_dist;
-    launch.a.crc_tab = c->d_tabs.as<uint32_t>();
-    return batch_status(deflate_batch_run(c->batch, &c->d_in.p, &c->d_in.cap, ordered_stream(c), c->ev0, c->ev1, in, out,
-                                          items, results, n, flags, launch, &c->last_ms));
+    return deflate_batch_launch(c, launch, in, out, items, results, n, chunk_len, flags);
 }
 
 int ndfl_deflate_batch_multi(ndfl_ctx* c, const uint8_t* in, uint64_t in_size, uint8_t* out, uint64_t out_size,
@@ -472,7 +477,7 @@ int ndfl_deflate_batch_multi(ndfl_ctx* c, const uint8_t* in, uint64_t in_size, u
         if (strats[k].kind == NDFL_KIND_UNCOMPRESSED) continue;
         if (strats[k].kind != NDFL_KIND_LZ77 || !lz77_tuple_valid(desc_tuple(strats[k]))) return NDFL_E_ARG;
     }
-    BatchMultiLaunch launch{c->batch_lz, c->knobs, items, dbm::Args{}};
+    BatchMultiLaunch launch{{c->batch_lz, c->knobs, items, dbm::Args{}}};
     // one Lz77Huffman alone, or several equal ones: nothing to choose, ndfl_deflate_batch_lz77's stream
     if (launch.set_candidates(strats, n_strats) == 1 && !(launch.a.c_flags[0] & dbm::C_STORED)) {
         const ndfl_strategy_desc& d = strats[launch.a.c_flags[0] >> 8];
@@ -480,11 +485,8 @@ int ndfl_deflate_batch_multi(ndfl_ctx* c, const uint8_t* in, uint64_t in_size, u
                                        d.min_dist, d.max_dist, chunk_len, hist_limit, flags);
     }
     if (const int e = deflate_batch_args(in, in_size, out, out_size, items, results, n, chunk_len, hist_limit)) return e;
-    HIPCHK(hipSetDevice(c->device));
-    launch.a.n = n; launch.a.chunk_len = chunk_len; launch.a.hist_limit = hist_limit;
-    launch.a.crc_tab = c->d_tabs.as<uint32_t>();
-    return batch_status(deflate_batch_run(c->batch, &c->d_in.p, &c->d_in.cap, ordered_stream(c), c->ev0, c->ev1, in, out,
-                                          items, results, n, flags, launch, &c->last_ms));
+    launch.a.hist_limit = hist_limit;
+    return deflate_batch_launch(c, launch, in, out, items, results, n, chunk_len, flags);
 }
 
 int ndfl_deflate_batch_binsplit(ndfl_ctx* c, const uint8_t* in, uint64_t in_size, uint8_t* out, uint64_t out_size,
@@ -498,14 +500,10 @@ int ndfl_deflate_batch_binsplit(ndfl_ctx* c, const uint8_t* in, uint64_t in_size
     if (const int e = deflate_batch_args(in, in_size, out, out_size, items, results, n, chunk_len, hist_limit)) return e;
     if (sub->kind != NDFL_KIND_LZ77) return NDFL_E_UNSUPPORTED;     // position-independent substrategies only
     if (!lz77_tuple_valid(desc_tuple(*sub))) return NDFL_E_ARG;
-    HIPCHK(hipSetDevice(c->device));
-    BatchBinsplitLaunch launch{c->batch_lz, c->knobs, items, dbsp::Args{}};
+    BatchBinsplitLaunch launch{{c->batch_lz, c->knobs, items, dbsp::Args{}}};
     launch.set_search(*sub);
-    launch.a.n = n; launch.a.chunk_len = chunk_len; launch.a.hist_limit = hist_limit;
-    launch.a.min_block = (uint32_t)min_block_len;
-    launch.a.crc_tab = c->d_tabs.as<uint32_t>();
-    return batch_status(deflate_batch_run(c->batch, &c->d_in.p, &c->d_in.cap, ordered_stream(c), c->ev0, c->ev1, in, out,
-                                          items, results, n, flags, launch, &c->last_ms));
+    launch.a.hist_limit = hist_limit; launch.a.min_block = (uint32_t)min_block_len;
+    return deflate_batch_launch(c, launch, in, out, items, results, n, chunk_len, flags);
 }
 
 int ndfl_inflate_range(ndfl_ctx* c, const uint8_t* in, uint64_t in_len, uint64_t start_bit, uint64_t end_bit,

@@ -2,45 +2,31 @@
 // launch, every chunk as the block of whichever substrategy takes the fewest bits
 // (ndfl_deflate_batch_multi, include/ndfl.h): MultiStrategy(strats...) of D/comp/MultiStrategy.java:31-57
 // over Lz77Huffman records and Uncompressed.SINGLETON (D/comp/Uncompressed.java:19-51).  The third of the
-// batch kernels, with the launch shape of its two siblings: a persistent grid of one-wave workgroups, an
-// atomic ticket over the stream indices, each stream encoded chunk by chunk, serially, by one wave that
-// waits on no other.  The stream frame, the bit buffer, the region stores and the checksum folding are
-// deflate_batch.hip's (dbat::), the link, search and parse and the token emitter deflate_batch_lz.hip's
-// (dblz::).
+// batch kernels: the stream frame is deflate_batch.hip's (dbat::), the chunk, its links, its searches and
+// its blocks' sizing and emit deflate_batch_lz.hip's (dblz::).  What is this file's: the candidates, the
+// best so far, and the stored block.
 //
 // The host hands the kernel CANDIDATES, not substrategies: exact duplicates are dropped (a later equal
 // one can never win), the Lz77Huffman ones are grouped by their (min_run, max_run, min_dist, max_dist),
 // a group's static one before its dynamic one, and each carries its index in the caller's list.  Per
-// chunk (= block):
-//   fold    the chunk's bytes into the stream's checksum: one walk, whichever block type wins;
-//   link    the chunk's positions, once (dblz::lz_chunk<LZ_LINK>), unless every search is literal-only;
-//   per candidate, in the host's order:
-//       the first of a group searches and parses (dblz::lz_chunk<LZ_SEARCH>) into the wave's CURRENT
-//       token list and the LDS histograms, which the rest of the group shares; hdist is copied to
-//       hdist0, because the code builder gives a single used distance code a dummy neighbour;
-//       build_block_codes<64, true> (static: the fixed codes), and the block's exact size: the header's
-//       bits plus, from the histograms, count x (code length + extra bits), end of block included (the
-//       dummy literal an empty block counts is taken off again: it is not emitted);
+// chunk (= block), after dblz::fold_and_link (one walk and one link pass, whichever block type wins),
+// per candidate, in the host's order:
+//   the first of a group searches (dblz::search_block) into the wave's CURRENT token list and the LDS
+//       histograms, which the rest of the group shares;
+//   dblz::size_block gives its codes, header and exact size;
 //       Uncompressed: 8 len + 40 max(ceil(len / 65535), 1) + ((13 - p) % 8 - 5) bits at bit position p;
-//       fewer bits than the best so far, or as many from an earlier index in the caller's list, makes
+//   fewer bits than the best so far, or as many from an earlier index in the caller's list, makes
 //       it the best: its two code tables, its header words and their bit count, and its token count are
 //       copied to the LDS's second set, and its token list becomes the one the next group's search does
-//       NOT write (the wave has two lists) -- so the best so far is never searched or built again;
-//   emit    the best: header, tokens and end of block from the second set (dblz::emit_tokens), or the
-//       stored blocks: 3 header bits, zero bits to the byte, LEN, NLEN, the bytes, at most 65,535 a
-//       block, BFINAL on the stream's last block only.  The bytes go through the same bit buffer, 64
-//       lanes x 4 bytes a step (they are byte aligned, a BitPut takes them as two 16-bit puts), so the
-//       flush, the out_cap clamp and the "no byte outside the region" rule stay one implementation.
+//       NOT write (the wave has two lists) -- so the best so far is never searched or built again.
+// Then the best is emitted: dblz::emit_block from the second set, or the stored blocks: 3 header bits,
+// zero bits to the byte, LEN, NLEN, the bytes, at most 65,535 a block, BFINAL on the stream's last block
+// only.  The bytes go through the same bit buffer, 64 lanes x 4 bytes a step (they are byte aligned, a
+// BitPut takes them as two 16-bit puts), so the flush, the out_cap clamp and the "no byte outside the
+// region" rule stay one implementation.
 //
-// Device memory of a wave (BatchLzScratch): two token lists and the link ring.  The chunk is linked
-// whole before its first position is searched, so the ring holds the chunk and its window at once:
-// the power of two >= min(the longest stream, hist_limit + chunk_len), at most 131,072 links.  At most
-// 256 KiB of links and 2 x 256 KiB of tokens per wave; with BATCH_LZ_BUDGET the grid never falls below
-// 341 waves.
-//
-// No scratch memory: everything is forced inline, no per-lane array is indexed by a variable, the lane
-// index is an opaque_lane() in every step, wave-uniform state is parked (dbat::to_v).  The candidates
-// are parked too: lane k holds candidate k's three words, read with readlane.
+// The candidates are parked as the rest of the wave-uniform state is: lane k holds candidate k's three
+// words, read with readlane.
 // D/ = src/io/nayuki/deflate/ in the reference
 #pragma once
 #include "deflate_batch_lz.hip"
@@ -59,21 +45,13 @@ using dbat::to_v;
 constexpr uint32_t MAXC = 8;                  // candidates (= substrategies) at most
 // a candidate's flags; its index in the caller's list is flags >> 8
 constexpr uint32_t C_STORED = 1, C_DYNAMIC = 2, C_SEARCH = 4;   // C_SEARCH: the first of its group
-constexpr uint32_t RING_MAX = 131072;         // link ring entries: >= 32,768 + 65,536
 
-struct Args : dbat::FrameArgs {
-    uint32_t hist_limit;
+struct Args : dblz::LzArgs {  // (two token lists per wave)
     uint32_t n_cand;          // 1..MAXC
     uint32_t c_flags[MAXC];
     uint32_t c_run[MAXC];     // min_run | max_run << 16
     uint32_t c_dist[MAXC];    // min_dist | max_dist << 16 (literal only: 1 | 0 << 16, no distance at all)
-    int32_t has_lz;           // some candidate is not C_STORED
     int32_t link;             // some candidate has a distance in its window: the chunks are linked
-    const uint32_t* crc_tab;  // as dblz::Args
-    uint16_t* ring;           // ring_mask + 1 links per wave
-    uint32_t ring_mask;
-    uint32_t* toks;           // 2 x tok_cap tokens per wave
-    uint32_t tok_cap;         // >= min(chunk_len, longest in_len)
 };
 
 // LDS of one wave: 22,424 bytes, 7 waves per CU (160 KiB / 22,424 = 7.3).
@@ -82,8 +60,6 @@ struct Lds : dblz::Lds {
     uint32_t b_dist[32];
     uint32_t b_hdr[HDRW];     // and its header words
 };
-
-using dblz::token_bits;       // a block's exact size from its histograms (shared with deflate_batch_binsplit.hip)
 
 // The chunk's len_c bytes at cp as stored blocks (D/comp/Uncompressed.java:32-46).  The walk's own
 // values are parked across make_room (v_cp, v_len_c, v_final: parked by the caller).
@@ -133,11 +109,8 @@ ndfl_deflate_batch_multi_kernel(dbm::Args a) {
     using namespace dbm;
     __shared__ __attribute__((aligned(16))) Lds S;
     const dbat::Frame f = dbat::park_frame(a);
-    const uint64_t v_tab = to_v((uint64_t)(uintptr_t)a.crc_tab);
-    const uint64_t v_ring = to_v((uint64_t)(uintptr_t)(a.ring + (size_t)blockIdx.x * ((size_t)a.ring_mask + 1)));
-    const uint64_t v_toks = to_v((uint64_t)(uintptr_t)(a.toks + (size_t)blockIdx.x * 2 * a.tok_cap));
-    const uint32_t v_mask = to_v(a.ring_mask), v_tcap = to_v(a.tok_cap);
-    const uint32_t v_hist = to_v(a.hist_limit), v_ncand = to_v(a.n_cand), v_link = to_v((uint32_t)(a.link != 0));
+    const dblz::Wave w = dblz::park_wave(a, 2);
+    const uint32_t v_tcap = to_v(a.tok_cap), v_ncand = to_v(a.n_cand), v_link = to_v((uint32_t)(a.link != 0));
     // candidate k in lane k
     uint32_t v_cf = 0, v_cr = 0, v_cd = 0;
     {
@@ -149,32 +122,11 @@ ndfl_deflate_batch_multi_kernel(dbm::Args a) {
     for (;;) {
         dbat::Stream st;
         if (!dbat::claim_stream(S, f, st)) break;
-        // the running state, all of it started afresh for the stream (as ndfl_deflate_batch_lz_kernel)
         BitOut bo = dbat::begin_stream(S, f, st);
-        uint32_t v_fill = to_v(0u), v_cb = to_v(0u);
-        uint64_t v_cs = to_v((uint64_t)0);
-        for (uint32_t j = (uint32_t)opaque_lane(); j < dblz::NHEAD / 2; j += 64)
-            ((uint32_t*)S.head)[j] = dblz::HNONE << 16 | dblz::HNONE;
-        for (;;) {
+        dblz::LzState z = dblz::begin_lz(S);
+        do {
             __syncthreads();
-            {
-                const uint64_t cs = to_s(v_cs), len = to_s(st.v_len);
-                const uint32_t len_c = (uint32_t)min((uint64_t)to_s(f.v_chunk_len), len - cs);
-                const uint64_t hs = cs - min((uint64_t)to_s(v_hist), cs);      // chunk 0 has no history
-                const uint8_t* P = (const uint8_t*)(uintptr_t)(to_s(st.v_src) + hs);
-                const uint32_t rc0 = (uint32_t)(cs - hs);
-                const uint32_t rend = (uint32_t)min(len - hs, (uint64_t)rc0 + len_c + 8);
-                uint32_t ck = to_s(st.v_ck);
-                dblz::fold_chunk(v_tab, P + rc0, len_c, to_s(st.v_kind), ck);
-                st.v_ck = to_v(ck);
-                if (to_s(v_link)) {                               // (literal-only searches follow no link)
-                    const dblz::Search none{0u, 0u, 0u, 0u};
-                    uint32_t cb = to_s(v_cb);
-                    dblz::lz_chunk<dblz::LZ_LINK>(S, none, P, rc0, len_c, rend, (uint32_t)hs,
-                                                  (uint16_t*)(uintptr_t)to_s(v_ring), to_s(v_mask), nullptr, true, cb);
-                    v_cb = to_v(cb + len_c);
-                }
-            }
+            dblz::fold_and_link(S, f, st, w, z, to_s(v_link) != 0);
             __syncthreads();                                          // the chunk's links
             // the best candidate so far: its bits and index, its header's bits, its token count and list
             uint32_t v_bbits = to_v(0xFFFFFFFFu), v_bidx = to_v(0xFFFFFFFFu), v_bhb = to_v(0u), v_bntok = to_v(0u);
@@ -185,45 +137,22 @@ ndfl_deflate_batch_multi_kernel(dbm::Args a) {
                 const uint32_t v_cfk = to_v((uint32_t)__builtin_amdgcn_readlane((int)v_cf, (int)to_s(v_k)));
                 uint32_t v_bits, v_hb = to_v(0u);
                 if (to_s(v_cfk) & C_STORED) {
-                    const uint64_t cs = to_s(v_cs);
-                    const uint32_t len_c = (uint32_t)min((uint64_t)to_s(f.v_chunk_len), to_s(st.v_len) - cs);
+                    const uint32_t len_c = dblz::chunk_view(f, st, w, z.v_cs).len_c;
                     const uint32_t nblk = max((len_c + 65534u) / 65535u, 1u);
-                    v_bits = to_v(8 * len_c + 40 * nblk + ((13u - (to_s(v_fill) & 7u)) & 7u) - 5u);
+                    v_bits = to_v(8 * len_c + 40 * nblk + ((13u - (to_s(z.v_fill) & 7u)) & 7u) - 5u);
                 } else {
                     if (to_s(v_cfk) & C_SEARCH) {
                         v_csel = to_v(to_s(v_bsel) ^ 1u);             // not the best's list
-                        dbat::begin_block_hist(S);
-                        __syncthreads();
-                        const uint64_t cs = to_s(v_cs), len = to_s(st.v_len);
-                        const uint32_t len_c = (uint32_t)min((uint64_t)to_s(f.v_chunk_len), len - cs);
-                        const uint64_t hs = cs - min((uint64_t)to_s(v_hist), cs);
-                        const uint8_t* P = (const uint8_t*)(uintptr_t)(to_s(st.v_src) + hs);
-                        const uint32_t rc0 = (uint32_t)(cs - hs);
-                        const uint32_t rend = (uint32_t)min(len - hs, (uint64_t)rc0 + len_c + 8);
                         const uint32_t cr = (uint32_t)__builtin_amdgcn_readlane((int)v_cr, (int)to_s(v_k));
                         const uint32_t cd = (uint32_t)__builtin_amdgcn_readlane((int)v_cd, (int)to_s(v_k));
                         const dblz::Search sp{cr & 0xFFFFu, cr >> 16, cd & 0xFFFFu, cd >> 16};
-                        uint32_t* toks = (uint32_t*)(uintptr_t)to_s(v_toks) + (size_t)to_s(v_csel) * to_s(v_tcap);
-                        uint32_t nocb = 0;
-                        v_ntok = to_v(dblz::lz_chunk<dblz::LZ_SEARCH>(S, sp, P, rc0, len_c, rend, (uint32_t)hs,
-                                                                      (uint16_t*)(uintptr_t)to_s(v_ring), to_s(v_mask),
-                                                                      toks, true, nocb));
-                        dbat::end_block_hist(S, len_c);
-                        __syncthreads();                              // the histograms and the token list
-                        {
-                            const int lane = opaque_lane();
-                            if (lane < 32) S.scr.hdist0[lane] = S.scr.hdist[lane];
-                        }
-                        __syncthreads();
+                        const dblz::Range whole{0u, dblz::chunk_view(f, st, w, z.v_cs).len_c};
+                        v_ntok = to_v(dblz::search_block(S, f, st, w, z.v_cs, sp, whole,
+                                                         dblz::toks_of(w) + (size_t)to_s(v_csel) * to_s(v_tcap)));
                     }
-                    {
-                        const bool is_final = to_s(st.v_len) - to_s(v_cs) <= (uint64_t)to_s(f.v_chunk_len);
-                        v_hb = to_v(build_block_codes<64, true>(S.scr, (to_s(v_cfk) & C_DYNAMIC) != 0, is_final, S.litCode,
-                                                                S.distCode));
-                    }
-                    // (an empty block's dummy literal is counted and not emitted)
-                    const bool empty = to_s(v_cs) >= to_s(st.v_len);
-                    v_bits = to_v(to_s(v_hb) + token_bits(S) - (empty ? rfl(S.litCode[0]) >> 16 : 0u));
+                    const dblz::ChunkView c = dblz::chunk_view(f, st, w, z.v_cs);
+                    const dblz::BlockSize b = dblz::size_block(S, (to_s(v_cfk) & C_DYNAMIC) != 0, c.is_final, c.len_c == 0);
+                    v_hb = b.v_hb; v_bits = b.v_bits;
                 }
                 {
                     const uint32_t bits = to_s(v_bits), idx = to_s(v_cfk) >> 8;
@@ -242,12 +171,10 @@ ndfl_deflate_batch_multi_kernel(dbm::Args a) {
                 __syncthreads();
             }
             // ---- the best one's block ---------------------------------------------------------------
-            bo.fill = to_s(v_fill);
+            bo.fill = to_s(z.v_fill);
             if (to_s(v_bstored)) {
-                const uint64_t cs = to_s(v_cs), len = to_s(st.v_len);
-                const uint32_t len_c = (uint32_t)min((uint64_t)to_s(f.v_chunk_len), len - cs);
-                put_stored(bo, to_v(to_s(st.v_src) + cs), to_v(len_c),
-                           to_v((uint32_t)(len - cs <= (uint64_t)to_s(f.v_chunk_len))));
+                const dblz::ChunkView c = dblz::chunk_view(f, st, w, z.v_cs);
+                put_stored(bo, to_v((uint64_t)(uintptr_t)(c.P + c.rc0)), to_v(c.len_c), to_v((uint32_t)c.is_final));
             } else {
                 {
                     const int lane = opaque_lane();
@@ -256,32 +183,21 @@ ndfl_deflate_batch_multi_kernel(dbm::Args a) {
                     for (int t = lane; t < HDRW; t += 64) S.scr.hdr()[t] = S.b_hdr[t];
                 }
                 __syncthreads();
-                dbat::put_header(S, bo, to_s(v_bhb));
-                dblz::emit_tokens(S, bo, (const uint32_t*)(uintptr_t)to_s(v_toks) + (size_t)to_s(v_bsel) * to_s(v_tcap),
-                                  to_s(v_bntok));
-                dbat::put_eob(S, bo);
+                dblz::emit_block(S, bo, to_s(v_bhb), dblz::toks_of(w) + (size_t)to_s(v_bsel) * to_s(v_tcap), to_s(v_bntok));
             }
-            {
-                const uint64_t cs = to_s(v_cs);
-                v_cs = to_v(cs + min((uint64_t)to_s(f.v_chunk_len), to_s(st.v_len) - cs));
-            }
-            v_fill = to_v(bo.fill);
-            if (to_s(v_cs) >= to_s(st.v_len)) break;
-        }
-        dbat::finish_stream(f, st, bo, v_fill);
+            z.v_fill = to_v(bo.fill);
+        } while (dblz::advance_chunk(f, st, w, z));
+        dbat::finish_stream(f, st, bo, z.v_fill);
     }
 }
 
 // ---- host side ------------------------------------------------------------------------------------
-// batch_run's launcher for ndfl_deflate_batch_multi_kernel.
-struct BatchMultiLaunch {
-    BatchLzScratch& Z;
-    const Knobs& knobs;
-    const ndfl_member_item* items;       // host
-    dbm::Args a;                          // n, chunk_len, hist_limit, the candidates, crc_tab; deflate_batch_run sets `in`
-    uint32_t grid = 0;
+static constexpr char BATCH_MULTI_LABEL[] = "deflate batch multi";
+
+// batch_run's launcher for ndfl_deflate_batch_multi_kernel: chunks linked whole, two token lists.
+struct BatchMultiLaunch : BatchLzLaunchT<dbm::Args, ndfl_deflate_batch_multi_kernel, true, 2, BATCH_MULTI_LABEL> {
     // The caller's substrategies (validated) as the kernel's candidates.  Returns their number; c_flags[0] >> 8
-    // is the index of the first one's substrategy.
+    // is the index of the first one's substrategy.  With no Lz77Huffman among them the wave needs no memory.
     uint32_t set_candidates(const ndfl_strategy_desc* strats, uint32_t n_strats) {
         struct C { uint32_t flags, run, dist; };
         std::vector<C> cs;
@@ -293,10 +209,9 @@ struct BatchMultiLaunch {
                 c.flags |= dbm::C_STORED;
             } else {
                 if (d.dynamic) c.flags |= dbm::C_DYNAMIC;
-                // the literal-only form searches a window with no distance in it: nothing is ever a run
-                const bool lit = d.min_run == 0;
-                c.run = lit ? 3u | 258u << 16 : (uint32_t)d.min_run | (uint32_t)d.max_run << 16;
-                c.dist = lit ? 1u : (uint32_t)d.min_dist | (uint32_t)d.max_dist << 16;
+                const dblz::Search sp = search_of(d);
+                c.run = sp.min_run | sp.max_run << 16;
+                c.dist = sp.min_dist | sp.max_dist << 16;
             }
             bool dup = false;
             for (const C& e : cs) dup = dup || ((e.flags & 0xFFu) == (c.flags & 0xFFu) && e.run == c.run && e.dist == c.dist);
@@ -307,7 +222,7 @@ struct BatchMultiLaunch {
                 groups.push_back({c.run, c.dist});
         }
         uint32_t m = 0;
-        a.has_lz = !groups.empty();
+        n_lists = groups.empty() ? 0u : 2u;
         a.link = 0;
         for (const auto& g : groups) a.link |= (g.second >> 16) >= (g.second & 0xFFFFu);
         for (const C& c : cs)
@@ -325,30 +240,5 @@ struct BatchMultiLaunch {
         }
         a.n_cand = m;
         return m;
-    }
-    // Before the launch is timed: sizes the wave's ring and two token lists from the batch, lowers the
-    // grid to the budget and grows the scratch (first use only).
-    int prepare() {
-        size_t per_wave = 0;
-        uint32_t ring = 64;
-        if (a.has_lz) {
-            uint64_t longest = 0;
-            for (uint32_t i = 0; i < a.n; i++) longest = std::max(longest, items[i].in_len);
-            const uint64_t span = std::min<uint64_t>(longest, (uint64_t)a.hist_limit + a.chunk_len);
-            while (ring < dbm::RING_MAX && ring < span) ring <<= 1;
-            a.tok_cap = (uint32_t)std::max<uint64_t>(64, std::min<uint64_t>(a.chunk_len, longest));
-            per_wave = (size_t)ring * 2 + (size_t)a.tok_cap * 8;
-        }
-        grid = batch_grid<ndfl_deflate_batch_multi_kernel>(a.n, knobs, "deflate batch multi", per_wave, BATCH_LZ_BUDGET);
-        if (per_wave) INF_CHK(inf_ensure(&Z.d_mem, &Z.d_mem_cap, (size_t)grid * per_wave));
-        a.toks = (uint32_t*)Z.d_mem;
-        a.ring = (uint16_t*)((char*)Z.d_mem + (size_t)grid * a.tok_cap * 8); a.ring_mask = ring - 1;
-        return 0;
-    }
-    int operator()(hipStream_t s, uint8_t* d_out, const ndfl_member_item* d_items, ndfl_deflate_result* d_res,
-                   uint32_t* d_ticket) {
-        a.out = d_out; a.items = d_items; a.results = d_res; a.ticket = d_ticket;
-        hipLaunchKernelGGL(ndfl_deflate_batch_multi_kernel, dim3(grid), dim3(64), 0, s, a);
-        return 0;
     }
 };

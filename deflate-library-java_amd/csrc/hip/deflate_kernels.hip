@@ -101,7 +101,7 @@ __device__ __forceinline__ void run_sym(uint32_t run, uint32_t& sym, uint32_t& n
     else if (run == 258) { sym = 285; ne = 0; ex = 0; }
     else {
         uint32_t r = run - 3;
-        ne = 29 - __clz(r);
+        ne = 29 - __builtin_clz(r);           // (r >= 8: no zero case to guard, whatever else shares the translation unit)
         sym = (ne << 2) + (r >> ne) + 257;
         ex = r & ((1u << ne) - 1);
     }

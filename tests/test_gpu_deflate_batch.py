@@ -11,7 +11,6 @@ per step, the chunk length), at the run lengths where the closed-form parse chan
 0..3 after whole 258s, with and without the lead literal).
 """
 import concurrent.futures
-import ctypes
 import functools
 import gzip
 import random
@@ -22,8 +21,8 @@ import pytest
 import adversarial_hist as A
 import deflate_batch_harness as H
 import oracle_lib as O
-from deflate_batch_harness import (ADLER32, CRC32, E_ARG, E_CAPACITY, E_UNSUPPORTED, FILL, GZIP, NONE, RAW, ZLIB,
-                                   checksum, ctx, mixed, one_wave, pack_inputs, salad, trailer)  # noqa: F401 (fixtures)
+from deflate_batch_harness import (ADLER32, CRC32, E_ARG, E_UNSUPPORTED, GZIP, NONE, RAW, ZLIB, checksum, ctx, mixed, one_wave,
+                                   pack_inputs, salad, trailer)  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -45,6 +44,13 @@ def oracle(buf, strategy="RLE_DYNAMIC", chunk_len=65536, hist_limit=32768):
 def raw(ctx, in_addr, in_size, out_addr, out_size, recs, cfg, flags):
     """ndfl_deflate_batch; cfg: (strategy, chunk_len, hist_limit)."""
     return ctx.deflate_batch_raw(in_addr, in_size, out_addr, out_size, recs, *cfg, flags)
+
+
+def c_call(ctx, in_addr, in_size, out_addr, out_size, items, results, n, cfg):
+    import ndfl
+    strategy, chunk_len, hist_limit = cfg
+    return ndfl._lib.load().ndfl_deflate_batch(ctx._h, in_addr, in_size, out_addr, out_size, items, results, n,
+                                               ndfl.STRATEGIES.get(strategy, strategy), chunk_len, hist_limit, 0)
 
 
 member = functools.partial(H.member, oracle)
@@ -130,18 +136,7 @@ def layout_items():
 def test_layout_touching_regions_every_residue(ctx):
     """Regions that touch, with out_off at every residue mod 16 (the members' lengths shift them, and a
     leading pad of 0..15 bytes shifts all of them), and `out` itself at an odd address."""
-    cfg = ("RLE_DYNAMIC", 65536, 32768)
-    items = layout_items()
-    seen = set()
-    for pad in range(16):
-        regions, off = [], pad
-        for buf, fmt, _ in items:
-            n = len(member(buf, fmt, cfg)[0])
-            regions.append((off, n))
-            seen.add(off % 16)
-            off += n
-        res, out, _ = run(ctx, items, cfg, regions=regions, out_size=off + 5, out_shift=1 if pad % 2 else 0)
-        check(items, cfg, res, out, regions, f"pad {pad}")
+    seen = H.touching_regions(raw, oracle, ctx, layout_items(), ("RLE_DYNAMIC", 65536, 32768), range(16), lambda pad: pad % 2)
     assert seen == set(range(16))
 
 
@@ -176,15 +171,8 @@ def test_capacity(ctx, fmt):
     rng = random.Random(9)
     left, mid, right = salad(rng, 777), mixed(rng, 4000), mixed(rng, 1500)
     R = len(member(mid, fmt, cfg)[0])
-    caps = [0, 1, R - 1, R] + ([R - 4, R - 3, R - 2] if fmt == ZLIB else [])
-    items, cl = [], []
-    for cap in caps:                        # all cases in one call: left | mid (cap) | right | left | mid ...
-        items += [(left, GZIP, NONE), (mid, fmt, CRC32), (right, RAW, ADLER32)]
-        cl += [len(member(left, GZIP, cfg)[0]), cap, len(member(right, RAW, cfg)[0])]
-    res = run_check(ctx, items, cfg, "capacity", caps=cl)
-    for k, cap in enumerate(caps):
-        assert res[3 * k + 1][0] == (0 if cap >= R else E_CAPACITY) and res[3 * k + 1][2] == R
-        assert res[3 * k][0] == 0 and res[3 * k + 2][0] == 0
+    H.capacity_layout(raw, oracle, ctx, cfg, left, mid, right, fmt,
+                      [0, 1, R - 1, R] + ([R - 4, R - 3, R - 2] if fmt == ZLIB else []))
 
 
 def test_checksums_and_trailers(ctx):
@@ -265,74 +253,20 @@ def test_more_streams_than_waves(ctx):
 
 
 def test_device_pointers_on_the_callers_stream(ctx):
-    """Input and output are torch tensors; the input is produced by a torch kernel on the current stream
-    immediately before the call, with no synchronize, and the output is read by torch right after."""
-    import torch
-    import ndfl
-    cfg = ("RLE_DYNAMIC", 65536, 32768)
-    items = reuse_items()[:60] + layout_items()
-    host_res, host_out, regions = run(ctx, items, cfg)
-    check(items, cfg, host_res, host_out, regions, "host")
-    packed, offs = pack_inputs(items)
-    recs = [(io, len(buf), o, c, fmt, kind) for (buf, fmt, kind), io, (o, c) in zip(items, offs, regions)]
-    n = len(packed)
-    # the device input is computed on the GPU: the packed bytes XOR 0x5A, XORed back by a torch kernel
-    masked = torch.frombuffer(bytearray(bytes(x ^ 0x5A for x in packed)), dtype=torch.uint8).cuda()
-    for shift in (0, 1):                                           # `in` and `out` at an odd address too
-        d_out = torch.full((len(host_out) + shift,), FILL, dtype=torch.uint8, device="cuda")
-        d_in = torch.empty(n + shift, dtype=torch.uint8, device="cuda")
-        d_in[shift:] = torch.bitwise_xor(masked, 0x5A)             # queued on the current stream, not waited for
-        res = ctx.deflate_batch_raw(d_in.data_ptr() + shift, n, d_out.data_ptr() + shift, len(host_out), recs, *cfg,
-                                    ndfl.IN_DEVICE | ndfl.OUT_DEVICE)
-        got = bytes(d_out.cpu().numpy())
-        assert res == host_res, shift
-        assert got[shift:] == host_out and got[:shift] == bytes([FILL]) * shift, shift
-    assert ctx.last_kernel_ms() > 0
+    H.device_pointers_on_the_callers_stream(raw, oracle, ctx, reuse_items()[:60] + layout_items(), ("RLE_DYNAMIC", 65536, 32768))
 
 
 def test_arguments(ctx):
-    import ndfl
-    L = ndfl._lib.load()
-    s = b"abcdef" * 10
-    src = ctypes.create_string_buffer(s, len(s))
-    out = ctypes.create_string_buffer(bytes([FILL]) * 256, 256)
-    a_in, a_out = ctypes.addressof(src), ctypes.addressof(out)
     ok = ("RLE_DYNAMIC", 65536, 32768)
-    assert ctx.deflate_batch_raw(a_in, len(s), a_out, 256, [], *ok, 0) == []
-    assert L.ndfl_deflate_batch(ctx._h, None, 0, None, 0, None, None, 0, 3, 65536, 32768, 0) == 0
-    one = [(0, len(s), 0, 100, RAW, NONE)]
-    res = (ndfl._lib.DeflateResult * 1)()
-    arr = (ndfl._lib.MemberItem * 1)(ndfl._lib.MemberItem(*one[0]))
-    before = bytes(res)
-    for args in ((None, len(s), a_out, 256, arr, res), (a_in, len(s), None, 256, arr, res),
-                 (a_in, len(s), a_out, 256, None, res), (a_in, len(s), a_out, 256, arr, None)):
-        assert L.ndfl_deflate_batch(ctx._h, *args, 1, 3, 65536, 32768, 0) == E_ARG
-    cases = [(E_ARG, items, ok) for items in (
-        [(0, len(s) + 1, 0, 100, RAW, NONE)], [(len(s) + 1, 0, 0, 100, RAW, NONE)], [(0, len(s), 200, 57, RAW, NONE)],
-        [(0, len(s), 257, 0, RAW, NONE)], [(0, len(s), 0, 100, RAW, NONE), (0, len(s), 99, 100, RAW, NONE)],
-        [(0, len(s), 50, 10, RAW, NONE), (0, len(s), 0, 100, RAW, NONE)], [(0, len(s), 1 << 63, 1 << 63, RAW, NONE)],
-        [(0, len(s), 0, 100, 3, NONE)], [(0, len(s), 0, 100, RAW, 3)])]
-    cases += [(E_ARG, one, ("RLE_DYNAMIC", 0, 32768)), (E_UNSUPPORTED, one, ("RLE_DYNAMIC", 65537, 32768)),
-              (E_ARG, one, ("RLE_DYNAMIC", 65536, 32769)), (E_UNSUPPORTED, one, ("FULL_DYNAMIC", 65536, 32768)),
-              (E_UNSUPPORTED, one, ("FULL_STATIC", 65536, 32768)), (E_UNSUPPORTED, one, ("UNCOMPRESSED", 65536, 32768)),
-              (E_ARG, one, (7, 65536, 32768))]
-    for code, items, cfg in cases:
-        with pytest.raises(ndfl.NdflError) as e:
-            ctx.deflate_batch_raw(a_in, len(s), a_out, 256, items, *cfg, 0)
-        assert e.value.code == code, (items, cfg)
-        assert out.raw == bytes([FILL]) * 256, (items, cfg)
-    # the raw call leaves `results` untouched on an error
-    assert L.ndfl_deflate_batch(ctx._h, a_in, len(s), a_out, 256, arr, res, 1, 5, 65536, 32768, 0) == E_UNSUPPORTED
-    assert L.ndfl_deflate_batch(ctx._h, a_in, len(s), a_out, 256, arr, res, 1, 3, 0, 32768, 0) == E_ARG
-    assert bytes(res) == before and out.raw == bytes([FILL]) * 256
-    # regions that only touch, and an empty region inside another, are fine
-    items = [(0, len(s), 0, 60, RAW, NONE), (0, len(s), 60, 60, RAW, NONE), (0, 0, 30, 0, RAW, NONE)]
-    got = ctx.deflate_batch_raw(a_in, len(s), a_out, 256, items, *ok, 0)
-    comp, bits = oracle(s)
-    empty, ebits = oracle(b"")
-    assert got == [(0, 0, len(comp), bits), (0, 0, len(comp), bits), (E_CAPACITY, 0, len(empty), ebits)]
-    assert out.raw[:len(comp)] == comp and out.raw[60:60 + len(comp)] == comp
-    assert out.raw[len(comp):60] == bytes([FILL]) * (60 - len(comp)) and out.raw[60 + len(comp):] == bytes([FILL]) * (196 - len(comp))
+
+    def own_cases(one):
+        return [(E_ARG, one, ("RLE_DYNAMIC", 0, 32768)), (E_UNSUPPORTED, one, ("RLE_DYNAMIC", 65537, 32768)),
+                (E_ARG, one, ("RLE_DYNAMIC", 65536, 32769)), (E_UNSUPPORTED, one, ("FULL_DYNAMIC", 65536, 32768)),
+                (E_UNSUPPORTED, one, ("FULL_STATIC", 65536, 32768)), (E_UNSUPPORTED, one, ("UNCOMPRESSED", 65536, 32768)),
+                (E_ARG, one, (7, 65536, 32768))]
+
+    a = H.argument_rules(raw, c_call, ctx, ok, own_cases)
+    H.regions_that_only_touch(raw, oracle, ctx, ok, a)
 
 
 @pytest.mark.parametrize("strategy", STRATEGIES)

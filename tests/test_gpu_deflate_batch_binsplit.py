@@ -24,13 +24,12 @@ import pytest
 import adversarial_hist as AH
 import deflate_batch_harness as H
 import oracle_lib as O
-import test_gpu_deflate_batch_lz as LZB
-from deflate_batch_harness import (ADLER32, CRC32, E_ARG, E_CAPACITY, E_UNSUPPORTED, FILL, GZIP, NONE, RAW, ZLIB,
-                                   checksum, ctx, one_wave, pack_inputs, salad, trailer)  # noqa: F401 (fixtures)
+from deflate_batch_harness import (ADLER32, CRC32, E_ARG, E_UNSUPPORTED, GZIP, NONE, RAW, ZLIB, ctx, one_wave, raws, salad,
+                                   trailer)  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
 
-FS, FD = LZB.FULL_STATIC, LZB.FULL_DYNAMIC
+FS, FD = H.FULL_STATIC, H.FULL_DYNAMIC
 RLE_DYNAMIC = (True, 3, 258, 1, 1)
 LITERAL_DYNAMIC = (True, 0, 0, 0, 0)
 ODD = (True, 4, 32, 2, 1024)
@@ -48,8 +47,9 @@ def oracle(buf, sub=FD, min_block_len=100, chunk_len=65536, hist_limit=32768):
 
 
 def desc(sub):
+    """The StrategyDesc record of an Lz77Huffman tuple (None and ready-made records pass through)."""
     import ndfl
-    return ndfl._lib.StrategyDesc(0, *map(int, sub))
+    return sub if sub is None or isinstance(sub, ndfl._lib.StrategyDesc) else ndfl._lib.StrategyDesc(0, *map(int, sub))
 
 
 def raw(ctx, in_addr, in_size, out_addr, out_size, recs, cfg, flags):
@@ -63,7 +63,13 @@ member = functools.partial(H.member, oracle)
 run = functools.partial(H.run, raw, oracle)
 check = functools.partial(H.check, oracle)
 run_check = functools.partial(H.run_check, raw, oracle)
-raws = LZB.raws
+
+
+def c_call(ctx, in_addr, in_size, out_addr, out_size, items, results, n, cfg):
+    import ndfl
+    sub = desc(cfg[0])
+    return ndfl._lib.load().ndfl_deflate_batch_binsplit(ctx._h, in_addr, in_size, out_addr, out_size, items, results, n,
+                                                        None if sub is None else ctypes.byref(sub), cfg[1], cfg[2], cfg[3], 0)
 
 
 def nblocks(buf, *cfg):
@@ -87,7 +93,7 @@ EVEN, UNEVEN = (16, 256), (13, 333)      # 4,096 bytes: even halvings; 4,329: ha
 def lz_end_bits(ctx, bufs, cfg):
     """end_bits of the same buffers under ndfl_deflate_batch_lz77 with cfg's tuple, chunk_len and hist_limit."""
     sub, _, chunk_len, hist_limit = cfg
-    return [r[3] for r in H.run_check(LZB.raw, LZB.oracle, ctx, raws(bufs), (sub, chunk_len, hist_limit), "unsplit")]
+    return [r[3] for r in H.run_check(H.lz_raw, H.lz_oracle, ctx, raws(bufs), (sub, chunk_len, hist_limit), "unsplit")]
 
 
 @pytest.mark.parametrize("min_block_len", [1, 100, 300, 1100])
@@ -112,7 +118,7 @@ def test_depth_counts_of_the_oracle():
     a = ladder(*EVEN)
     assert [nblocks(a, FD, m) for m in (1, 100, 300, 1100)] == [16, 16, 8, 2]
     assert nblocks(ladder(*UNEVEN), FD, 100) >= 16
-    assert len(oracle(a)[0]) < 0.7 * len(LZB.oracle(a)[0])         # this is where BinarySplit pays
+    assert len(oracle(a)[0]) < 0.7 * len(H.lz_oracle(a)[0])         # this is where BinarySplit pays
 
 
 def static_splitters():
@@ -142,7 +148,7 @@ def test_halves_must_be_longer_than_min_block_len(ctx):
     rng = random.Random(0x513)
     buf = letters(rng, 257, b"01") + letters(rng, 256)
     assert nblocks(buf, FD, 255) == 2 and nblocks(buf, FD, 256) == 1
-    assert len(oracle(buf, FD, 255)[0]) < len(oracle(buf, FD, 256)[0]) == len(LZB.oracle(buf)[0])
+    assert len(oracle(buf, FD, 255)[0]) < len(oracle(buf, FD, 256)[0]) == len(H.lz_oracle(buf)[0])
     for m in (255, 256):
         run_check(ctx, raws([buf]), (FD, m, 65536, 32768), "min(f, s) > min_block_len")
 
@@ -219,20 +225,12 @@ def test_capacity(ctx, fmt):
     assert len(blocks) >= 8
     inside_second = (blocks[1]["bit"] + blocks[1]["end_bit"]) // 16
     R = len(member(mid, fmt, DEFAULT)[0])
-    caps = [0, inside_second, R - 1, R]
     assert 0 < inside_second < R - 1
-    items, cl = [], []
-    for cap in caps:
-        items += [(left, GZIP, NONE), (mid, fmt, CRC32), (right, RAW, ADLER32)]
-        cl += [len(member(left, GZIP, DEFAULT)[0]), cap, len(member(right, RAW, DEFAULT)[0])]
-    res = run_check(ctx, items, DEFAULT, "capacity", caps=cl)
-    for k, cap in enumerate(caps):
-        assert res[3 * k + 1][0] == (0 if cap >= R else E_CAPACITY) and res[3 * k + 1][2] == R
-        assert res[3 * k][0] == 0 and res[3 * k + 2][0] == 0
+    H.capacity_layout(raw, oracle, ctx, DEFAULT, left, mid, right, fmt, [0, inside_second, R - 1, R])
 
 
 def layout_items():
-    items = LZB.layout_items()
+    items = H.layout_items()
     for k, b in enumerate((ladder(*EVEN), ladder(*UNEVEN), ladder(5, 100), ladder(3, 211))):
         items.insert(5 * k + 1, (b, (GZIP, RAW, ZLIB)[k % 3], (CRC32, NONE, ADLER32)[k % 3]))
     return items
@@ -242,104 +240,37 @@ def layout_items():
 def test_touching_regions_at_every_alignment(ctx, shift):
     items = layout_items()
     assert sum(nblocks(b) > 1 for b, _, _ in items) >= 4
-    for pad in range(4):
-        regions, off = [], pad
-        for buf, fmt, _ in items:
-            n = len(member(buf, fmt, DEFAULT)[0])
-            regions.append((off, n))
-            off += n
-        res, out, _ = run(ctx, items, DEFAULT, regions=regions, out_size=off + 5, out_shift=shift)
-        check(items, DEFAULT, res, out, regions, f"shift {shift} pad {pad}")
+    H.touching_regions(raw, oracle, ctx, items, DEFAULT, range(4), shift)
 
 
 def test_device_pointers_on_the_callers_stream(ctx):
-    import torch
-    import ndfl
-    items = list(mixed_batch()) + layout_items()
-    host_res, host_out, regions = run(ctx, items, DEFAULT)
-    check(items, DEFAULT, host_res, host_out, regions, "host")
-    packed, offs = pack_inputs(items)
-    recs = [(io, len(buf), o, c, fmt, kind) for (buf, fmt, kind), io, (o, c) in zip(items, offs, regions)]
-    n = len(packed)
-    masked = torch.frombuffer(bytearray(bytes(x ^ 0x5A for x in packed)), dtype=torch.uint8).cuda()
-    for shift in (0, 1):
-        d_out = torch.full((len(host_out) + shift,), FILL, dtype=torch.uint8, device="cuda")
-        d_in = torch.empty(n + shift, dtype=torch.uint8, device="cuda")
-        d_in[shift:] = torch.bitwise_xor(masked, 0x5A)             # queued on the current stream, not waited for
-        res = raw(ctx, d_in.data_ptr() + shift, n, d_out.data_ptr() + shift, len(host_out), recs, DEFAULT,
-                  ndfl.IN_DEVICE | ndfl.OUT_DEVICE)
-        got = bytes(d_out.cpu().numpy())
-        assert res == host_res, shift
-        assert got[shift:] == host_out and got[:shift] == bytes([FILL]) * shift, shift
-    assert ctx.last_kernel_ms() > 0
+    H.device_pointers_on_the_callers_stream(raw, oracle, ctx, list(mixed_batch()) + layout_items(), DEFAULT)
 
 
 def test_arguments(ctx):
     import ndfl
     L = ndfl._lib.load()
     D = ndfl._lib.StrategyDesc
-    s = b"abcdef" * 10
-    src = ctypes.create_string_buffer(s, len(s))
-    out = ctypes.create_string_buffer(bytes([FILL]) * 256, 256)
-    a_in, a_out = ctypes.addressof(src), ctypes.addressof(out)
     fd = desc(FD)
-    ok = (fd, 100, 65536, 32768)
+    ok = (FD, 100, 65536, 32768)
 
-    def call(items, cfg, flags=0):
-        return ctx.deflate_batch_binsplit_raw(a_in, len(s), a_out, 256, items, cfg[0], cfg[1], cfg[2], cfg[3], flags)
+    def own_cases(one):
+        stored, seven = D(1, 0, 0, 0, 0, 0), D(7, 1, 3, 258, 1, 32768)
+        cases = [(E_ARG, one, (None, 100, 65536, 32768)), (E_ARG, one, (fd, 0, 65536, 32768)),
+                 (E_ARG, one, (fd, -1, 65536, 32768)), (E_ARG, one, (fd, 100, 0, 32768)),
+                 (E_UNSUPPORTED, one, (fd, 100, 65537, 32768)), (E_ARG, one, (fd, 100, 65536, 32769)),
+                 (E_UNSUPPORTED, one, (stored, 100, 65536, 32768)), (E_UNSUPPORTED, one, (seven, 100, 65536, 32768)),
+                 # ndfl_deflate_chunks_binsplit's order: min_block_len before the frame, the frame before the kind,
+                 # the kind before the tuple
+                 (E_ARG, one, (stored, 0, 65537, 32768)), (E_UNSUPPORTED, one, (stored, 100, 65537, 32768)),
+                 (E_ARG, one, (stored, 100, 0, 32768)), (E_ARG, one, (stored, 100, 65536, 32769)),
+                 (E_UNSUPPORTED, one, (D(1, 1, 2, 258, 1, 32768), 100, 65536, 32768))]
+        return cases + [(E_ARG, one, (desc(bad), 100, 65536, 32768)) for bad in H.BAD_TUPLES]
 
-    # n == 0: nothing is looked at
-    assert call([], ok) == []
-    assert L.ndfl_deflate_batch_binsplit(ctx._h, None, 0, None, 0, None, None, 0, ctypes.byref(fd), 100, 65536, 32768, 0) == 0
+    a = H.argument_rules(raw, c_call, ctx, ok, own_cases)
+    # n == 0: nothing is looked at, not the substrategy, min_block_len, chunk_len or hist_limit either
     assert L.ndfl_deflate_batch_binsplit(ctx._h, None, 0, None, 0, None, None, 0, None, 0, 0, 40000, 0) == 0
-    assert out.raw == bytes([FILL]) * 256
-    one = [(0, len(s), 0, 100, RAW, NONE)]
-    res = (ndfl._lib.DeflateResult * 1)()
-    arr = (ndfl._lib.MemberItem * 1)(ndfl._lib.MemberItem(*one[0]))
-    before = bytes(res)
-    for args in ((None, len(s), a_out, 256, arr, res), (a_in, len(s), None, 256, arr, res),
-                 (a_in, len(s), a_out, 256, None, res), (a_in, len(s), a_out, 256, arr, None)):
-        assert L.ndfl_deflate_batch_binsplit(ctx._h, *args, 1, ctypes.byref(fd), 100, 65536, 32768, 0) == E_ARG
-    stored, seven = D(1, 0, 0, 0, 0, 0), D(7, 1, 3, 258, 1, 32768)
-    cases = [(E_ARG, items, ok) for items in (
-        [(0, len(s) + 1, 0, 100, RAW, NONE)], [(len(s) + 1, 0, 0, 100, RAW, NONE)], [(0, len(s), 200, 57, RAW, NONE)],
-        [(0, len(s), 257, 0, RAW, NONE)], [(0, len(s), 0, 100, RAW, NONE), (0, len(s), 99, 100, RAW, NONE)],
-        [(0, len(s), 50, 10, RAW, NONE), (0, len(s), 0, 100, RAW, NONE)], [(0, len(s), 1 << 63, 1 << 63, RAW, NONE)],
-        [(0, len(s), 0, 100, 3, NONE)], [(0, len(s), 0, 100, RAW, 3)])]
-    cases += [(E_ARG, one, (None, 100, 65536, 32768)), (E_ARG, one, (fd, 0, 65536, 32768)),
-              (E_ARG, one, (fd, -1, 65536, 32768)), (E_ARG, one, (fd, 100, 0, 32768)),
-              (E_UNSUPPORTED, one, (fd, 100, 65537, 32768)), (E_ARG, one, (fd, 100, 65536, 32769)),
-              (E_UNSUPPORTED, one, (stored, 100, 65536, 32768)), (E_UNSUPPORTED, one, (seven, 100, 65536, 32768)),
-              # ndfl_deflate_chunks_binsplit's order: min_block_len before the frame, the frame before the kind,
-              # the kind before the tuple
-              (E_ARG, one, (stored, 0, 65537, 32768)), (E_UNSUPPORTED, one, (stored, 100, 65537, 32768)),
-              (E_ARG, one, (stored, 100, 0, 32768)), (E_ARG, one, (stored, 100, 65536, 32769)),
-              (E_UNSUPPORTED, one, (D(1, 1, 2, 258, 1, 32768), 100, 65536, 32768))]
-    for bad in [(True, 2, 258, 1, 32768), (True, 3, 259, 1, 32768), (True, 5, 4, 1, 10), (True, 3, 258, 0, 10),
-                (True, 3, 258, 1, 32769), (True, 3, 258, 10, 9)]:
-        cases += [(E_ARG, one, (desc(bad), 100, 65536, 32768))]
-    for code, items, cfg in cases:
-        with pytest.raises(ndfl.NdflError) as e:
-            call(items, cfg)
-        assert e.value.code == code, (items, cfg)
-        assert out.raw == bytes([FILL]) * 256, (items, cfg)
-        # the same call with a result array of this test's: untouched too
-        arr_k = (ndfl._lib.MemberItem * len(items))(*[ndfl._lib.MemberItem(*it) for it in items])
-        res_k = (ndfl._lib.DeflateResult * len(items))()
-        before_k = bytes(res_k)
-        sub_k = None if cfg[0] is None else ctypes.byref(cfg[0])
-        assert L.ndfl_deflate_batch_binsplit(ctx._h, a_in, len(s), a_out, 256, arr_k, res_k, len(items), sub_k, cfg[1],
-                                             cfg[2], cfg[3], 0) == code, (items, cfg)
-        assert bytes(res_k) == before_k and out.raw == bytes([FILL]) * 256, (items, cfg)
-    assert bytes(res) == before and out.raw == bytes([FILL]) * 256
-    # regions that only touch, and an empty region inside another, are fine
-    items = [(0, len(s), 0, 60, RAW, NONE), (0, len(s), 60, 60, RAW, NONE), (0, 0, 30, 0, RAW, NONE)]
-    got = call(items, ok)
-    comp, bits = oracle(s)
-    empty, ebits = oracle(b"")
-    assert got == [(0, 0, len(comp), bits), (0, 0, len(comp), bits), (E_CAPACITY, 0, len(empty), ebits)]
-    assert out.raw[:len(comp)] == comp and out.raw[60:60 + len(comp)] == comp
-    assert out.raw[len(comp):60] == bytes([FILL]) * (60 - len(comp)) and out.raw[60 + len(comp):] == bytes([FILL]) * (196 - len(comp))
+    H.regions_that_only_touch(raw, oracle, ctx, ok, a)
 
 
 def test_against_the_chunked_encoder(ctx):
@@ -377,4 +308,4 @@ def test_python_routing(ctx):
             ctx.deflate_batch(bufs[:2], strategy)
         assert e.value.code == E_UNSUPPORTED
     # the other routes are as they were
-    assert ctx.deflate_batch(bufs[:7], LH.FULL_DYNAMIC)[6][:2] == LZB.oracle(bufs[6])
+    assert ctx.deflate_batch(bufs[:7], LH.FULL_DYNAMIC)[6][:2] == H.lz_oracle(bufs[6])

@@ -13,7 +13,6 @@ carry from one stream into the next.
 
 U = Uncompressed, FS = FULL_STATIC, FD = FULL_DYNAMIC, T3 = (U, FS, FD).
 """
-import ctypes
 import functools
 import gzip
 import itertools
@@ -25,15 +24,14 @@ import pytest
 import adversarial_hist as AH
 import deflate_batch_harness as H
 import oracle_lib as O
-import test_gpu_deflate_batch_lz as LZB
 import test_gpu_lz77 as LZ
-from deflate_batch_harness import (ADLER32, CRC32, E_ARG, E_CAPACITY, E_UNSUPPORTED, FILL, GZIP, NONE, RAW, ZLIB,
-                                   checksum, ctx, mixed, one_wave, pack_inputs, salad, trailer)  # noqa: F401 (fixtures)
+from deflate_batch_harness import (ADLER32, CRC32, E_ARG, E_UNSUPPORTED, FILL, GZIP, NONE, RAW, ZLIB, checksum, ctx, mixed,
+                                   one_wave, raws, salad, trailer)  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 U = "UNCOMPRESSED"
-FS, FD = LZB.FULL_STATIC, LZB.FULL_DYNAMIC
+FS, FD = H.FULL_STATIC, H.FULL_DYNAMIC
 RLE_DYNAMIC = (True, 3, 258, 1, 1)
 LITERAL_STATIC, LITERAL_DYNAMIC = (False, 0, 0, 0, 0), (True, 0, 0, 0, 0)
 T3 = (U, FS, FD)
@@ -50,9 +48,10 @@ def oracle(buf, subs=T3, chunk_len=65536, hist_limit=32768):
 
 
 def descs(subs):
+    """StrategyDesc records of U / Lz77Huffman tuples (ready-made records pass through)."""
     import ndfl
     D = ndfl._lib.StrategyDesc
-    return [D(1, 0, 0, 0, 0, 0) if s == U else D(0, *map(int, s)) for s in subs]
+    return [s if isinstance(s, D) else D(1, 0, 0, 0, 0, 0) if s == U else D(0, *map(int, s)) for s in subs]
 
 
 def raw(ctx, in_addr, in_size, out_addr, out_size, recs, cfg, flags):
@@ -66,7 +65,14 @@ member = functools.partial(H.member, oracle)
 run = functools.partial(H.run, raw, oracle)
 check = functools.partial(H.check, oracle)
 run_check = functools.partial(H.run_check, raw, oracle)
-raws = LZB.raws
+
+
+def c_call(ctx, in_addr, in_size, out_addr, out_size, items, results, n, cfg):
+    import ndfl
+    subs = descs(cfg[0])
+    arr = (ndfl._lib.StrategyDesc * max(1, len(subs)))(*subs)
+    return ndfl._lib.load().ndfl_deflate_batch_multi(ctx._h, in_addr, in_size, out_addr, out_size, items, results, n, arr,
+                                                     len(subs), cfg[1], cfg[2], 0)
 
 
 def btypes(comp):
@@ -159,7 +165,7 @@ EIGHT = FIVE + (FS, LITERAL_DYNAMIC, (False, 3, 258, 64, 32767))
 
 
 def tuple_buffers():
-    return LZB.edge_buffers()[::7] + [b for b in LZB.chain_buffers() if len(b) < 10000] + LZ.inputs(12)[::2]
+    return H.edge_buffers()[::7] + [b for b in H.chain_buffers() if len(b) < 10000] + LZ.inputs(12)[::2]
 
 
 # the two lists after them take the host's short cuts: equal substrategies that leave one Lz77Huffman (forwarded to
@@ -171,7 +177,7 @@ def test_tuples(ctx, subs):
 
 
 def single_oracle(buf, subs, chunk_len, hist_limit):
-    return LZB.oracle(buf, subs[0], chunk_len, hist_limit)
+    return H.lz_oracle(buf, subs[0], chunk_len, hist_limit)
 
 
 @pytest.mark.parametrize("params", [s for s in EIGHT if s != U])
@@ -196,12 +202,12 @@ def test_best_so_far_survives_a_loser_and_loses_to_a_winner(ctx):
 @pytest.mark.parametrize("hist_limit", [0, 1, 100, 32768])
 @pytest.mark.parametrize("chunk_len", [1, 7, 259, 1000, 65536])
 def test_chunk_ends_and_history(ctx, chunk_len, hist_limit):
-    run_check(ctx, raws(LZB.chunk_edge_buffers()), (T3, chunk_len, hist_limit), "chunk end")
+    run_check(ctx, raws(H.chunk_edge_buffers()), (T3, chunk_len, hist_limit), "chunk end")
 
 
 def test_wave_reuse_one_wave(one_wave):
     """Nothing of the stream before -- its best so far, its histograms, its stored block's position -- leaks."""
-    items = LZB.reuse_items()
+    items = H.reuse_items()
     assert len(items) == 300
     for cfg in (DEFAULT, ((U, FD), 259, 32768)):
         run_check(one_wave, items, cfg, "one wave")
@@ -215,21 +221,13 @@ def test_capacity(ctx, fmt):
     left, right = salad(rng, 777), salad(rng, 1500)
     for mid in (mixed(rng, 4000), rng.randbytes(300)):
         R = len(member(mid, fmt, DEFAULT)[0])
-        caps = [0, 1, R - 1, R]
-        items, cl = [], []
-        for cap in caps:
-            items += [(left, GZIP, NONE), (mid, fmt, CRC32), (right, RAW, ADLER32)]
-            cl += [len(member(left, GZIP, DEFAULT)[0]), cap, len(member(right, RAW, DEFAULT)[0])]
-        res = run_check(ctx, items, DEFAULT, "capacity", caps=cl)
-        for k, cap in enumerate(caps):
-            assert res[3 * k + 1][0] == (0 if cap >= R else E_CAPACITY) and res[3 * k + 1][2] == R
-            assert res[3 * k][0] == 0 and res[3 * k + 2][0] == 0
+        H.capacity_layout(raw, oracle, ctx, DEFAULT, left, mid, right, fmt, [0, 1, R - 1, R])
     assert btypes(oracle(mid)[0]) == [0]
 
 
 def layout_items():
     rng = random.Random(78)
-    items = LZB.layout_items()
+    items = H.layout_items()
     for k, n in enumerate((5, 64, 255, 256, 257, 300, 1025)):          # stored members between the others
         items.insert(4 * k + 1, (rng.randbytes(n), (GZIP, RAW, ZLIB)[k % 3], (CRC32, NONE, ADLER32)[k % 3]))
     return items
@@ -239,111 +237,51 @@ def layout_items():
 def test_touching_regions_at_every_alignment(ctx, shift):
     items = layout_items()
     assert sum(btypes(oracle(b)[0]) == [0] for b, _, _ in items) >= 5
-    for pad in range(4):
-        regions, off = [], pad
-        for buf, fmt, _ in items:
-            n = len(member(buf, fmt, DEFAULT)[0])
-            regions.append((off, n))
-            off += n
-        res, out, _ = run(ctx, items, DEFAULT, regions=regions, out_size=off + 5, out_shift=shift)
-        check(items, DEFAULT, res, out, regions, f"shift {shift} pad {pad}")
+    H.touching_regions(raw, oracle, ctx, items, DEFAULT, range(4), shift)
 
 
 def test_device_pointers_on_the_callers_stream(ctx):
-    import torch
-    import ndfl
-    items = LZB.reuse_items()[:60] + layout_items()
-    host_res, host_out, regions = run(ctx, items, DEFAULT)
-    check(items, DEFAULT, host_res, host_out, regions, "host")
-    packed, offs = pack_inputs(items)
-    recs = [(io, len(buf), o, c, fmt, kind) for (buf, fmt, kind), io, (o, c) in zip(items, offs, regions)]
-    n = len(packed)
-    masked = torch.frombuffer(bytearray(bytes(x ^ 0x5A for x in packed)), dtype=torch.uint8).cuda()
-    for shift in (0, 1):
-        d_out = torch.full((len(host_out) + shift,), FILL, dtype=torch.uint8, device="cuda")
-        d_in = torch.empty(n + shift, dtype=torch.uint8, device="cuda")
-        d_in[shift:] = torch.bitwise_xor(masked, 0x5A)             # queued on the current stream, not waited for
-        res = raw(ctx, d_in.data_ptr() + shift, n, d_out.data_ptr() + shift, len(host_out), recs, DEFAULT,
-                  ndfl.IN_DEVICE | ndfl.OUT_DEVICE)
-        got = bytes(d_out.cpu().numpy())
-        assert res == host_res, shift
-        assert got[shift:] == host_out and got[:shift] == bytes([FILL]) * shift, shift
-    assert ctx.last_kernel_ms() > 0
+    H.device_pointers_on_the_callers_stream(raw, oracle, ctx, H.reuse_items()[:60] + layout_items(), DEFAULT)
 
 
 def test_arguments(ctx):
     import ndfl
     L = ndfl._lib.load()
     D = ndfl._lib.StrategyDesc
-    s = b"abcdef" * 10
-    src = ctypes.create_string_buffer(s, len(s))
-    out = ctypes.create_string_buffer(bytes([FILL]) * 256, 256)
-    a_in, a_out = ctypes.addressof(src), ctypes.addressof(out)
     t3 = descs(T3)
-    ok = (t3, 65536, 32768)
+    ok = (T3, 65536, 32768)
 
-    def call(items, cfg, flags=0):
-        return ctx.deflate_batch_multi_raw(a_in, len(s), a_out, 256, items, cfg[0], cfg[1], cfg[2], flags)
+    def own_cases(one):
+        # the frame; the strategies: none, too many, another kind; the six invalid tuples of test_gpu_lz77.py
+        cases = [(E_ARG, one, (t3, 0, 32768)), (E_UNSUPPORTED, one, (t3, 65537, 32768)), (E_ARG, one, (t3, 65536, 32769)),
+                 (E_ARG, one, ([], 65536, 32768)), (E_UNSUPPORTED, one, (descs((FD,)) * 9, 65536, 32768)),
+                 (E_ARG, one, ([D(1, 0, 0, 0, 0, 0), D(2, 1, 3, 258, 1, 32768)], 65536, 32768)),
+                 (E_ARG, one, (descs((U,)), 0, 32768)), (E_UNSUPPORTED, one, (descs((U,)), 65537, 32768)),
+                 (E_ARG, one, (descs((FD,)), 65536, 32769))]
+        for bad in H.BAD_TUPLES:
+            cases += [(E_ARG, one, (descs((U, bad)), 65536, 32768)), (E_ARG, one, (descs((bad,)), 65536, 32768)),
+                      (E_ARG, one, (descs((FS, FD, bad)), 65536, 32768))]
+        return cases
 
+    a = H.argument_rules(raw, c_call, ctx, ok, own_cases)
+    # n == 0 with no strategies either; a null list and a count of 0 with a list
     arr3 = (D * 3)(*t3)
-    assert call([], ok) == []
-    assert L.ndfl_deflate_batch_multi(ctx._h, None, 0, None, 0, None, None, 0, arr3, 3, 65536, 32768, 0) == 0
     assert L.ndfl_deflate_batch_multi(ctx._h, None, 0, None, 0, None, None, 0, None, 0, 65536, 32768, 0) == 0
-    assert out.raw == bytes([FILL]) * 256
-    one = [(0, len(s), 0, 100, RAW, NONE)]
     res = (ndfl._lib.DeflateResult * 1)()
-    arr = (ndfl._lib.MemberItem * 1)(ndfl._lib.MemberItem(*one[0]))
+    arr = (ndfl._lib.MemberItem * 1)(ndfl._lib.MemberItem(*a.one[0]))
     before = bytes(res)
-    for args in ((None, len(s), a_out, 256, arr, res), (a_in, len(s), None, 256, arr, res),
-                 (a_in, len(s), a_out, 256, None, res), (a_in, len(s), a_out, 256, arr, None)):
-        assert L.ndfl_deflate_batch_multi(ctx._h, *args, 1, arr3, 3, 65536, 32768, 0) == E_ARG
-    # the strategies: none, a null list, too many, another kind, the six invalid tuples of test_gpu_lz77.py
-    good = (a_in, len(s), a_out, 256, arr, res, 1)
+    good = (a.a_in, len(a.s), a.a_out, 256, arr, res, 1)
     assert L.ndfl_deflate_batch_multi(ctx._h, *good, arr3, 0, 65536, 32768, 0) == E_ARG
     assert L.ndfl_deflate_batch_multi(ctx._h, *good, None, 3, 65536, 32768, 0) == E_ARG
     nine = (D * 9)(*(descs((FD,)) * 9))
     assert L.ndfl_deflate_batch_multi(ctx._h, *good, nine, 9, 65536, 32768, 0) == E_UNSUPPORTED
-    cases = [(E_ARG, items, ok) for items in (
-        [(0, len(s) + 1, 0, 100, RAW, NONE)], [(len(s) + 1, 0, 0, 100, RAW, NONE)], [(0, len(s), 200, 57, RAW, NONE)],
-        [(0, len(s), 257, 0, RAW, NONE)], [(0, len(s), 0, 100, RAW, NONE), (0, len(s), 99, 100, RAW, NONE)],
-        [(0, len(s), 50, 10, RAW, NONE), (0, len(s), 0, 100, RAW, NONE)], [(0, len(s), 1 << 63, 1 << 63, RAW, NONE)],
-        [(0, len(s), 0, 100, 3, NONE)], [(0, len(s), 0, 100, RAW, 3)])]
-    cases += [(E_ARG, one, (t3, 0, 32768)), (E_UNSUPPORTED, one, (t3, 65537, 32768)), (E_ARG, one, (t3, 65536, 32769)),
-              (E_ARG, one, ([], 65536, 32768)), (E_UNSUPPORTED, one, (descs((FD,)) * 9, 65536, 32768)),
-              (E_ARG, one, ([D(1, 0, 0, 0, 0, 0), D(2, 1, 3, 258, 1, 32768)], 65536, 32768)),
-              (E_ARG, one, (descs((U,)), 0, 32768)), (E_UNSUPPORTED, one, (descs((U,)), 65537, 32768)),
-              (E_ARG, one, (descs((FD,)), 65536, 32769))]
-    for bad in [(True, 2, 258, 1, 32768), (True, 3, 259, 1, 32768), (True, 5, 4, 1, 10), (True, 3, 258, 0, 10),
-                (True, 3, 258, 1, 32769), (True, 3, 258, 10, 9)]:
-        cases += [(E_ARG, one, (descs((U, bad)), 65536, 32768)), (E_ARG, one, (descs((bad,)), 65536, 32768)),
-                  (E_ARG, one, (descs((FS, FD, bad)), 65536, 32768))]
-    for code, items, cfg in cases:
-        with pytest.raises(ndfl.NdflError) as e:
-            call(items, cfg)
-        assert e.value.code == code, (items, cfg)
-        assert out.raw == bytes([FILL]) * 256, (items, cfg)
-        # the same call with a result array of this test's: untouched too
-        arr_k = (ndfl._lib.MemberItem * len(items))(*[ndfl._lib.MemberItem(*it) for it in items])
-        res_k = (ndfl._lib.DeflateResult * len(items))()
-        before_k = bytes(res_k)
-        subs_k = (D * max(1, len(cfg[0])))(*cfg[0])
-        assert L.ndfl_deflate_batch_multi(ctx._h, a_in, len(s), a_out, 256, arr_k, res_k, len(items), subs_k, len(cfg[0]),
-                                          cfg[1], cfg[2], 0) == code, (items, cfg)
-        assert bytes(res_k) == before_k and out.raw == bytes([FILL]) * 256, (items, cfg)
-    assert bytes(res) == before and out.raw == bytes([FILL]) * 256
+    assert bytes(res) == before and a.out.raw == bytes([FILL]) * 256
     # ndfl_deflate_batch itself still refuses what this call is for
     for name in ("FULL_DYNAMIC", "UNCOMPRESSED"):
         with pytest.raises(ndfl.NdflError) as e:
-            ctx.deflate_batch_raw(a_in, len(s), a_out, 256, one, name, 65536, 32768, 0)
-        assert e.value.code == E_UNSUPPORTED and out.raw == bytes([FILL]) * 256
-    # regions that only touch, and an empty region inside another, are fine
-    items = [(0, len(s), 0, 60, RAW, NONE), (0, len(s), 60, 60, RAW, NONE), (0, 0, 30, 0, RAW, NONE)]
-    got = call(items, ok)
-    comp, bits = oracle(s)
-    empty, ebits = oracle(b"")
-    assert got == [(0, 0, len(comp), bits), (0, 0, len(comp), bits), (E_CAPACITY, 0, len(empty), ebits)]
-    assert out.raw[:len(comp)] == comp and out.raw[60:60 + len(comp)] == comp
-    assert out.raw[len(comp):60] == bytes([FILL]) * (60 - len(comp)) and out.raw[60 + len(comp):] == bytes([FILL]) * (196 - len(comp))
+            ctx.deflate_batch_raw(a.a_in, len(a.s), a.a_out, 256, a.one, name, 65536, 32768, 0)
+        assert e.value.code == E_UNSUPPORTED and a.out.raw == bytes([FILL]) * 256
+    H.regions_that_only_touch(raw, oracle, ctx, ok, a)
 
 
 def test_equals_the_one_stream_encoder(ctx):

@@ -131,3 +131,30 @@ def test_encoder_kernels_do_not_grow(kernel):
     assert k["sgpr_spill_count"] <= sspills, k
     assert k["vgpr_count"] <= vgprs, k
     assert k["group_segment_fixed_size"] <= lds, k
+
+
+# The four batched deflate kernels (deflate_batch*.hip): one wave per workgroup, everything forced inline,
+# wave-uniform state parked in VGPRs -- so no scratch and no spill of either kind, which their sources
+# claim and this asserts.  Measured before the LZ kernels' chunk layer (dblz::) was shared: 111, 122, 132
+# and 131 VGPRs, here rounded up to the allocation granule of 8; LDS is exact.  Upper bounds: smaller is
+# welcome.
+BATCH_DEFLATE_KERNEL_BOUNDS = {
+    # kernel: scratch B, vgpr spills, sgpr spills, vgprs, LDS B
+    "ndfl_deflate_batch_kernel": (0, 0, 0, 112, 12632),
+    "ndfl_deflate_batch_lz_kernel": (0, 0, 0, 128, 20824),
+    "ndfl_deflate_batch_multi_kernel": (0, 0, 0, 136, 22424),
+    "ndfl_deflate_batch_binsplit_kernel": (0, 0, 0, 136, 21016),
+}
+
+
+@needs_tools
+@pytest.mark.parametrize("kernel", sorted(BATCH_DEFLATE_KERNEL_BOUNDS))
+def test_batch_deflate_kernels_do_not_grow(kernel):
+    k = kernel_metadata()[kernel]
+    scratch, spills, sspills, vgprs, lds = BATCH_DEFLATE_KERNEL_BOUNDS[kernel]
+    print(kernel, k)
+    assert k["private_segment_fixed_size"] <= scratch, k
+    assert k["vgpr_spill_count"] <= spills, k
+    assert k["sgpr_spill_count"] <= sspills, k
+    assert k["vgpr_count"] <= vgprs, k
+    assert k["group_segment_fixed_size"] <= lds, k
