@@ -5,6 +5,7 @@
 #include "../hip/deflate_split.hip"
 #include "../hip/lz77_kernels.hip"
 #include "../hip/strategy_kernels.hip"
+#include "../hip/deflate_seg.hip"
 #include "../hip/inflate_kernels.hip"
 #include "../hip/inflate_batch.hip"
 #include "../hip/deflate_batch.hip"
@@ -20,6 +21,8 @@
 #include <vector>
 #include <functional>
 #include <map>
+#include <memory>
+#include <new>
 
 namespace {
 
@@ -83,6 +86,7 @@ struct ndfl_ctx {
     DevBuf d_in, d_out, d_status, d_ticket, d_edge_w, d_edge_v, d_crc, d_crc1, d_tabs, d_hostio;
     DevBuf d_hist, d_codes, d_off;  // split RLE/LITERAL pipeline: histograms, code records, offsets
     DevBuf d_lz, d_link, d_match;   // LZ77 path: staging [pad|hist|data], hash links, per-position matches
+    DevBuf d_segtab;                // ndfl_deflate_batch_chunked: the chunk table, then the stream table
     DevBuf d_mdata, d_mstreams[16], d_mbits[16], d_masm;   // strategy composition
     int ncu = 0;                    // the device's compute units (0: unknown)
     InflateScratch inf;
@@ -182,7 +186,7 @@ int ndfl_ctx_destroy(ndfl_ctx* c) {
     hipStreamSynchronize(c->stream);
     DevBuf* bufs[] = {&c->d_in, &c->d_out, &c->d_status, &c->d_ticket, &c->d_edge_w, &c->d_edge_v,
                       &c->d_crc, &c->d_crc1, &c->d_tabs, &c->d_hostio, &c->d_lz, &c->d_link, &c->d_match,
-                      &c->d_mdata, &c->d_masm, &c->d_hist, &c->d_codes, &c->d_off};
+                      &c->d_mdata, &c->d_masm, &c->d_hist, &c->d_codes, &c->d_off, &c->d_segtab};
     for (DevBuf* b : bufs) b->release();
     for (int k = 0; k < 16; k++) { c->d_mstreams[k].release(); c->d_mbits[k].release(); }
     c->inf.release();
@@ -397,6 +401,8 @@ static int deflate_batch_launch(ndfl_ctx* c, Launch& launch, const uint8_t* in, 
     return batch_status(deflate_batch_run(c->batch, &c->d_in.p, &c->d_in.cap, ordered_stream(c), c->ev0, c->ev1, in, out,
                                           items, results, n, flags, launch, &c->last_ms));
 }
+
+#include "ndfl_deflate_batch_chunked.cpp"
 
 extern "C" {
 

@@ -21,6 +21,7 @@
 // D/ = /root/reference/src/io/nayuki/deflate/
 #pragma once
 #include "huffman_build.hpp"
+#include "seg_tables.hpp"
 
 namespace {
 
@@ -111,8 +112,13 @@ __device__ __forceinline__ void run_sym(uint32_t run, uint32_t& sym, uint32_t& n
 // then its inclusive prefix published.  Lane i polls predecessor c-1-i, so 64 predecessors cost one
 // round trip; the closest inclusive prefix (PRE) ends the walk, aggregates (AGG) before it are
 // summed, and a not-yet-published predecessor closer than it re-polls.  Chunk ids come from a
-// ticket, so a workgroup only waits on workgroups that already started.  Result in ps.P.
-__device__ __forceinline__ void block_lookback(uint32_t c, uint64_t base_bit, uint64_t S, uint64_t* status, Persist& ps) {
+// ticket, so a workgroup only waits on workgroups that already started.  Result in ps.P.  SEG: the
+// chunk without a predecessor is not chunk 0 but its stream's first chunk (`first`), which has
+// published its inclusive prefix from base_bit, its stream's own base: a successor's walk ends there
+// and never reaches another stream's words.
+template <bool SEG = false>
+__device__ __forceinline__ void block_lookback(uint32_t c, uint64_t base_bit, uint64_t S, uint64_t* status, Persist& ps,
+                                               bool first = false) {
     const int tid = threadIdx.x;
     const int lane = tid & 63, wid = tid >> 6;
     if (wid == 0) {
@@ -120,7 +126,7 @@ __device__ __forceinline__ void block_lookback(uint32_t c, uint64_t base_bit, ui
         // one round trip; the closest inclusive prefix (PRE) ends the walk, aggregates (AGG)
         // before it are summed, and a not-yet-published predecessor closer than it re-polls.
         uint64_t P = base_bit;
-        if (c > 0) {
+        if (SEG ? !first : c > 0) {
             uint64_t acc = 0;
             int64_t base = (int64_t)c - 1;
             for (;;) {
@@ -180,9 +186,13 @@ __device__ __forceinline__ void put_end_of_block(uint32_t* obuf, uint32_t bitpos
 // code tables and header from the record, token bits at the precomputed offset).  obuf is the bit
 // buffer, under MODE_FUSED first the code-construction scratch with the histograms, whose header
 // words are kept in hdrw[HDRW] while the buffer is zeroed; MODE_HIST passes only the 1024 last bytes.
-template <int MODE>
+// SEG (the split passes only): the chunk's length, its history and its BFINAL come from its record
+// (seg_tables.hpp); a.in is the staged data, a.n its slots' total, a.chunk_off[c] an offset from the
+// chunk's own stream's base.
+template <int MODE, bool SEG = false>
 __device__ __forceinline__ void deflate_chunk(const Args& a, uint32_t* obuf, Persist& ps, uint32_t* hdrw = nullptr,
-                                              uint32_t* hl4 = nullptr, uint32_t* ctab = nullptr) {
+                                              uint32_t* hl4 = nullptr, uint32_t* ctab = nullptr, const SegTab t = SegTab{}) {
+    static_assert(!SEG || MODE != MODE_FUSED, "the one-kernel encoder is not segmented");
     HuffScr* scr = (HuffScr*)obuf;
     uint32_t* hlit = scr->hlit;
     uint32_t* hdist = scr->hdist;
@@ -205,10 +215,14 @@ __device__ __forceinline__ void deflate_chunk(const Args& a, uint32_t* obuf, Per
         if (a.crc_raw) ctab[tid] = a.crc_tab[tid];          // slicing-by-4 tables to LDS (DT == 1024)
     }
     __syncthreads();
-    const uint32_t c = ps.chunk;
+    uint32_t c = ps.chunk;
+    if constexpr (SEG) c = a.c0 + blockIdx.x;                       // (the same value, in a scalar register)
     const uint64_t cs = (uint64_t)c * a.chunk_len;
-    const uint32_t len_c = (uint32_t)min((uint64_t)a.chunk_len, a.n - cs);
-    const bool is_final = a.final_last && (c + 1 == a.nchunks);
+    uint32_t segf = 0;
+    if constexpr (SEG) segf = t.chunks[c].flags;
+    const uint32_t len_c = SEG ? t.chunks[c].len : (uint32_t)min((uint64_t)a.chunk_len, a.n - cs);
+    const bool is_final = SEG ? (segf & SEG_LAST) != 0 : a.final_last && (c + 1 == a.nchunks);
+    const bool first = SEG && (segf & SEG_FIRST) != 0;
     const uint8_t* src = a.in + cs;
 
     // ---- 1. load 64 bytes per lane into registers --------------------------------------------
@@ -299,8 +313,10 @@ __device__ __forceinline__ void deflate_chunk(const Args& a, uint32_t* obuf, Per
     };
     // ---- 2. run pieces ------------------------------------------------------------------------
     // a block inside its parent chunk always has the parent's earlier bytes as history
-    const bool has_prev0 = (cs % a.parent_len != 0) ? true : (c > 0) ? (a.hist_enabled != 0) : (a.prev_byte >= 0);
-    const uint32_t prev0 = (c > 0) ? (uint32_t)src[-1] : (uint32_t)(a.prev_byte & 0xFF);
+    const bool has_prev0 = SEG ? !first && a.hist_enabled != 0
+                               : (cs % a.parent_len != 0) ? true : (c > 0) ? (a.hist_enabled != 0) : (a.prev_byte >= 0);
+    const uint32_t prev0 = SEG ? (first ? 0u : (uint32_t)src[-1])
+                               : (c > 0) ? (uint32_t)src[-1] : (uint32_t)(a.prev_byte & 0xFF);
     uint64_t F = 0;
     if (vcnt > 0) {
         uint32_t prev = tid > 0 ? (uint32_t)lastb[tid - 1] : 0u;
@@ -599,7 +615,7 @@ _Pragma("unroll")
             (void)tp3a; (void)tp3b;
         }
     }
-    (void)is_final;
+    (void)is_final; (void)first;
     asm volatile("" :: "v"(pfv));
 }
 
@@ -620,6 +636,14 @@ ndfl_deflate_hist_kernel(Args a) {
     __shared__ Persist ps;
     deflate_chunk<MODE_HIST>(a, lastb, ps, nullptr, hl4, ctab);
 }
+extern "C" __global__ void __launch_bounds__(DT, 8)
+ndfl_deflate_hist_seg_kernel(Args a, SegTab t) {
+    __shared__ __attribute__((aligned(16))) uint32_t lastb[1024 / 4];
+    __shared__ __attribute__((aligned(16))) uint32_t hl4[HCOPY * HSTR];
+    __shared__ uint32_t ctab[1024];
+    __shared__ Persist ps;
+    deflate_chunk<MODE_HIST, true>(a, lastb, ps, nullptr, hl4, ctab, t);
+}
 
 // Split pipeline pass 4: token bits at the offset from ndfl_deflate_offsets_kernel.
 extern "C" __global__ void __launch_bounds__(DT, 8)
@@ -627,6 +651,12 @@ ndfl_deflate_emit_kernel(Args a) {
     __shared__ __attribute__((aligned(16))) uint32_t obuf[OUTW];
     __shared__ Persist ps;
     deflate_chunk<MODE_EMIT>(a, obuf, ps);
+}
+extern "C" __global__ void __launch_bounds__(DT, 8)
+ndfl_deflate_emit_seg_kernel(Args a, SegTab t) {
+    __shared__ __attribute__((aligned(16))) uint32_t obuf[OUTW];
+    __shared__ Persist ps;
+    deflate_chunk<MODE_EMIT, true>(a, obuf, ps, nullptr, nullptr, nullptr, t);
 }
 
 // Merge the boundary words: every word touched by more than one chunk is the OR of all of them.
@@ -661,18 +691,13 @@ ndfl_crc_combine_kernel(const uint32_t* crc_raw, uint32_t nchunks, uint32_t chun
     if ((threadIdx.x & 63) == 0 && acc) atomicXor(out_raw, acc);
 }
 
-// Standalone CRC-32 (raw, init 0) of a device buffer: one 1024-thread workgroup per 64 KiB
-// segment, combined by ndfl_crc_combine_kernel.  Used on the decompress side (gunzip trailer).
-extern "C" __global__ void __launch_bounds__(1024)
-ndfl_crc_segments_kernel(const uint8_t* in, uint64_t n, const uint32_t* crc_tab, const uint32_t* crc_x,
-                         uint32_t* seg_raw) {
-    __shared__ uint32_t red[16];
-    const uint32_t seg = blockIdx.x;
-    const uint64_t s0 = (uint64_t)seg * 65536;
-    const uint32_t len = (uint32_t)min((uint64_t)65536, n - s0);
+// The raw CRC (init 0) of the `len` <= 65536 bytes at `seg`, by 1024 threads (red: 16 words of LDS);
+// thread 0 has the result.
+__device__ __forceinline__ uint32_t crc_segment_raw(const uint8_t* seg, uint32_t len, const uint32_t* crc_tab,
+                                                    const uint32_t* crc_x, uint32_t* red) {
     const uint32_t t0 = threadIdx.x * 64;
     const int vcnt = (int)min(64u, len > t0 ? len - t0 : 0u);
-    const uint8_t* src = in + s0 + t0;
+    const uint8_t* src = seg + t0;
     uint32_t cr = 0;
     const uint32_t* T0 = crc_tab; const uint32_t* T1 = crc_tab + 256;
     const uint32_t* T2 = crc_tab + 512; const uint32_t* T3 = crc_tab + 768;
@@ -701,11 +726,23 @@ ndfl_crc_segments_kernel(const uint8_t* in, uint64_t n, const uint32_t* crc_tab,
     contrib = wave_xor(contrib);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = contrib;
     __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t x = 0;
+    uint32_t x = 0;
+    if (threadIdx.x == 0)
         for (int k = 0; k < 16; k++) x ^= red[k];
-        seg_raw[seg] = x;
-    }
+    return x;
+}
+
+// Standalone CRC-32 (raw, init 0) of a device buffer: one 1024-thread workgroup per 64 KiB
+// segment, combined by ndfl_crc_combine_kernel.  Used on the decompress side (gunzip trailer).
+extern "C" __global__ void __launch_bounds__(1024)
+ndfl_crc_segments_kernel(const uint8_t* in, uint64_t n, const uint32_t* crc_tab, const uint32_t* crc_x,
+                         uint32_t* seg_raw) {
+    __shared__ uint32_t red[16];
+    const uint32_t seg = blockIdx.x;
+    const uint64_t s0 = (uint64_t)seg * 65536;
+    const uint32_t len = (uint32_t)min((uint64_t)65536, n - s0);
+    const uint32_t x = crc_segment_raw(in + s0, len, crc_tab, crc_x, red);
+    if (threadIdx.x == 0) seg_raw[seg] = x;
 }
 
 // Multi-GPU seam step: a shard's bit stream, compressed at bit 0, is moved to bit `shift` (0..7)

@@ -29,15 +29,15 @@ __device__ __forceinline__ uint32_t dist_extra(uint32_t d) { return d >= 4 ? (d 
 
 // Pass 2: one wave builds one chunk's codes and header from its histograms (build_block_codes<64>,
 // huffman_build.hpp).  Writes the code record (codes, header bits, hdrBits) and the block size in
-// bits to a.status[c] (+ chunk_bits).
-extern "C" __global__ void __launch_bounds__(64)
-ndfl_deflate_codes_kernel(Args a) {
-    __shared__ __attribute__((aligned(16))) HuffScr S;
+// bits to a.status[c] (+ chunk_bits).  SEG: the chunk's length and BFINAL from its record.
+namespace {
+template <bool SEG>
+__device__ __forceinline__ void deflate_codes(const Args& a, HuffScr& S, const SegTab t = SegTab{}) {
     const uint32_t c = a.c0 + blockIdx.x;
     const int lane = threadIdx.x;
     const uint64_t cs = (uint64_t)c * a.chunk_len;
-    const uint32_t len_c = (uint32_t)min((uint64_t)a.chunk_len, a.n - cs);
-    const bool is_final = a.final_last && (c + 1 == a.nchunks);
+    const uint32_t len_c = SEG ? t.chunks[c].len : (uint32_t)min((uint64_t)a.chunk_len, a.n - cs);
+    const bool is_final = SEG ? (t.chunks[c].flags & SEG_LAST) != 0 : a.final_last && (c + 1 == a.nchunks);
     const uint32_t* h = a.hist_out + (uint64_t)c * HREC;
     uint32_t* rec = (uint32_t*)a.codes + (uint64_t)c * CREC;
     for (int i = lane; i < 288; i += 64) S.hlit[i] = h[i];
@@ -60,6 +60,18 @@ ndfl_deflate_codes_kernel(Args a) {
         if (a.chunk_bits) a.chunk_bits[c] = Sz;
     }
 }
+}  // namespace
+
+extern "C" __global__ void __launch_bounds__(64)
+ndfl_deflate_codes_kernel(Args a) {
+    __shared__ __attribute__((aligned(16))) HuffScr S;
+    deflate_codes<false>(a, S);
+}
+extern "C" __global__ void __launch_bounds__(64)
+ndfl_deflate_codes_seg_kernel(Args a, SegTab t) {
+    __shared__ __attribute__((aligned(16))) HuffScr S;
+    deflate_codes<true>(a, S, t);
+}
 
 // Pass 3: chunk c's global bit offset = base + sum of the sizes before it; total[0] = end bit.  Two
 // launches (ndfl_common.hpp scan_tile_*): the tile sums, then each tile's scan; grid = tiles.
@@ -72,4 +84,18 @@ ndfl_deflate_offsets_kernel(const uint64_t* sizes, uint32_t n, uint64_t base, ui
                             const uint64_t* part) {
     scan_tile_apply([&](uint32_t i) { return sizes[i]; }, [&](uint32_t i, uint64_t v) { off[i] = v; }, n, part, base,
                     total);
+}
+
+// Pass 3 under SEG, after the two launches above have scanned all chunks' sizes into `raw` (base 0):
+// the scan restarts at every stream's base.  Chunk k of stream s starts at bit 8 * obase[s] + raw[k] -
+// raw[first chunk of s] of the staged output; sizes[k] becomes the chunk's inclusive prefix there, as
+// a look-back would have published it (a stream's end is its last chunk's).
+extern "C" __global__ void __launch_bounds__(256)
+ndfl_deflate_offsets_seg_kernel(const uint64_t* raw, uint64_t* sizes, uint32_t n, SegTab t, uint64_t* off) {
+    const uint32_t k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= n) return;
+    const SegStream st = t.streams[t.chunks[k].stream];
+    const uint64_t o = 8 * st.obase + (raw[k] - raw[st.first_chunk]);
+    off[k] = o;
+    sizes[k] = ST_PRE | (o + sizes[k]);
 }

@@ -19,6 +19,7 @@
 //                             bits and the look-back/store shared with the RLE encoder.
 // D/ = /root/reference/src/io/nayuki/deflate/
 #include "ndfl_common.hpp"
+#include "seg_tables.hpp"
 
 namespace {
 
@@ -272,15 +273,31 @@ __device__ __forceinline__ uint32_t wave_max_dpp(uint32_t x) {
 }
 
 // A wave's current chunk and parent chunk along its path (positions only grow): no division per
-// search.  All wave-uniform.
+// search.  All wave-uniform.  SEG (seg_tables.hpp: every stream in a slot of whole chunks, so cs and ps
+// are what they were): the chunk's end and its stream's first byte come from the chunk's record.
+template <bool SEG>
 struct LzpBnd {
     uint64_t cs, ps;
-    __device__ __forceinline__ void init(const LzArgs& a, uint64_t q) {
+    uint64_t e, vs;                                // SEG only: the chunk's end, the stream's first byte
+    uint32_t k;                                    // SEG only: the chunk
+    __device__ __forceinline__ void record(const SegTab& t) {
+        e = cs + t.chunks[k].len;
+        vs = LZ_DS + t.chunks[k].start;
+    }
+    __device__ __forceinline__ void init(const LzArgs& a, const SegTab& t, uint64_t q) {
         cs = LZ_DS + ((q - LZ_DS) / a.chunk_len) * a.chunk_len;
         ps = LZ_DS + ((q - LZ_DS) / a.parent_len) * a.parent_len;
+        if constexpr (SEG) { k = (uint32_t)((q - LZ_DS) / a.chunk_len); record(t); }
     }
-    __device__ __forceinline__ void advance(const LzArgs& a, uint64_t q) {
-        while (q >= cs + a.chunk_len) cs += a.chunk_len;
+    __device__ __forceinline__ void advance(const LzArgs& a, const SegTab& t, uint64_t q) {
+        if constexpr (SEG) {
+            if (q >= cs + a.chunk_len) {
+                while (q >= cs + a.chunk_len) { cs += a.chunk_len; k++; }
+                record(t);
+            }
+        } else {
+            while (q >= cs + a.chunk_len) cs += a.chunk_len;
+        }
         while (q >= ps + a.parent_len) ps += a.parent_len;
     }
 };
@@ -295,15 +312,18 @@ struct LzpS {
 };
 
 // Wave-cooperative exact search at buffer position q (window-relative rq).  All lanes call with the
-// same q; returns the match word (run << 16 | dist - 1, or the literal byte).
-__device__ __forceinline__ uint32_t lzp_search(const LzArgs& a, const LzpS& S, int64_t wb0, uint64_t q, LzpBnd& bd,
-                                               uint32_t* st) {
+// same q; returns the match word (run << 16 | dist - 1, or the literal byte).  SEG: a position in a
+// slot's padding, past its chunk's end, is a literal (a path steps over the padding to the next chunk).
+template <bool SEG>
+__device__ __forceinline__ uint32_t lzp_search(const LzArgs& a, const SegTab& t, const LzpS& S, int64_t wb0, uint64_t q,
+                                               LzpBnd<SEG>& bd, uint32_t* st) {
     const int lane = threadIdx.x & 63;
     const uint32_t rq = (uint32_t)((int64_t)q - wb0);
-    bd.advance(a, q);
-    const uint64_t e = min(bd.cs + a.chunk_len, a.total);
+    bd.advance(a, t, q);
+    const uint64_t e = SEG ? bd.e : min(bd.cs + a.chunk_len, a.total);
+    if (SEG && q >= e) return lz_byte(S.wb, rq);
     const uint32_t maxlen = (uint32_t)min((uint64_t)a.max_run, e - q);
-    const uint64_t off = bd.ps - min((uint64_t)a.hist_limit, bd.ps - a.vstart);
+    const uint64_t off = bd.ps - min((uint64_t)a.hist_limit, bd.ps - (SEG ? bd.vs : a.vstart));
     const int64_t lo = max((int64_t)q - (int64_t)a.max_dist, (int64_t)off);
     const int64_t hi = (int64_t)q - (int64_t)a.min_dist;
     const uint32_t lit = lz_byte(S.wb, rq);
@@ -352,11 +372,11 @@ __device__ __forceinline__ uint32_t lzp_search(const LzArgs& a, const LzpS& S, i
     const uint32_t run = best >> 16;
     return run >= a.min_run ? (run << 16 | (rq - (best & 0xFFFFu) - 1)) : lit;
 }
-}  // namespace
-
-extern "C" __global__ void __launch_bounds__(1024)
-ndfl_lz_parse_match_kernel(LzArgs a, uint32_t lead_on) {
-    __shared__ __attribute__((aligned(16))) LzpS S;
+// One tile (the kernels below).  SEG: a.vstart = LZ_DS and a.total = the end of the last slot; the
+// sort takes every staged byte, a neighbour's and the zeroed padding too, and the search's window
+// bounds keep a stream to its own.
+template <bool SEG>
+__device__ __forceinline__ void lz_parse_match_tile(const LzArgs& a, uint32_t lead_on, LzpS& S, const SegTab tab = SegTab{}) {
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const uint64_t p0 = a.p_begin + (uint64_t)blockIdx.x * LZP_TILE;
     const uint64_t p1 = min(p0 + LZP_TILE, a.p_end);
@@ -414,10 +434,10 @@ ndfl_lz_parse_match_kernel(LzArgs a, uint32_t lead_on) {
     if (s_w < p1) {
         const bool chunk_start = ((p0 - LZ_DS) % a.chunk_len) == 0;
         uint64_t q = (w == 0 && lead_on && !chunk_start) ? q00 : s_w;
-        LzpBnd bd;
-        bd.init(a, q);
+        LzpBnd<SEG> bd;
+        bd.init(a, tab, q);
         while (q < e_w) {
-            const uint32_t m = lzp_search(a, S, wb0, q, bd, st);
+            const uint32_t m = lzp_search<SEG>(a, tab, S, wb0, q, bd, st);
             if (q >= s_w) {
                 const uint32_t t = (uint32_t)(q - p0);
                 if (lane == 0) { a.match[q - a.p_begin] = m; atomicOr(&S.vis[t >> 5], 1u << (t & 31)); }
@@ -438,11 +458,11 @@ ndfl_lz_parse_match_kernel(LzArgs a, uint32_t lead_on) {
             if (ent >= ev) x = ent;                     // the true path passes over this segment
             else if (!((S.vis[ent >> 5] >> (ent & 31)) & 1u)) {
                 uint32_t t = ent;
-                LzpBnd bd;
-                bd.init(a, p0 + t);
+                LzpBnd<SEG> bd;
+                bd.init(a, tab, p0 + t);
                 while (t < ev && !((S.vis[t >> 5] >> (t & 31)) & 1u)) {
                     const uint64_t q = p0 + t;
-                    const uint32_t m = lzp_search(a, S, wb0, q, bd, st);
+                    const uint32_t m = lzp_search<SEG>(a, tab, S, wb0, q, bd, st);
                     if (lane == 0) { a.match[q - a.p_begin] = m; atomicOr(&S.vis[t >> 5], 1u << (t & 31)); }
                     t += step_of(m);
                 }
@@ -458,6 +478,18 @@ ndfl_lz_parse_match_kernel(LzArgs a, uint32_t lead_on) {
         atomicAdd(&a.stats[5], (unsigned long long)(wall_clock64() - tk2)); atomicAdd(&a.stats[6], 1ull);
     }
 }
+}  // namespace
+
+extern "C" __global__ void __launch_bounds__(1024)
+ndfl_lz_parse_match_kernel(LzArgs a, uint32_t lead_on) {
+    __shared__ __attribute__((aligned(16))) LzpS S;
+    lz_parse_match_tile<false>(a, lead_on, S);
+}
+extern "C" __global__ void __launch_bounds__(1024)
+ndfl_lz_parse_match_seg_kernel(LzArgs a, uint32_t lead_on, SegTab t) {
+    __shared__ __attribute__((aligned(16))) LzpS S;
+    lz_parse_match_tile<true>(a, lead_on, S, t);
+}
 
 // Exact search at one position from global memory (the encode kernel's rare fallback for a true-path
 // position the parse-driven search did not reach): every distance of the window, 64 per step, the
@@ -468,13 +500,16 @@ struct LzGlob {
     uint64_t total, vstart;
     uint32_t chunk_len, parent_len, hist_limit, min_run, max_run, min_dist, max_dist;
 };
-__device__ __noinline__ uint32_t lz_match_global(const LzGlob& g, uint64_t q) {
+// SEG (q inside its chunk): the chunk's end and the stream's first byte from the chunk's record.
+template <bool SEG>
+__device__ __forceinline__ uint32_t lz_match_global_at(const LzGlob& g, uint64_t q, const SegChunk* chunks) {
     const int lane = threadIdx.x & 63;
     const uint64_t cs = LZ_DS + ((q - LZ_DS) / g.chunk_len) * g.chunk_len;
-    const uint64_t e = min(cs + g.chunk_len, g.total);
+    const SegChunk* rec = SEG ? chunks + (q - LZ_DS) / g.chunk_len : nullptr;
+    const uint64_t e = SEG ? cs + rec->len : min(cs + g.chunk_len, g.total);
     const uint32_t maxlen = (uint32_t)min((uint64_t)g.max_run, e - q);
     const uint64_t ps = LZ_DS + ((q - LZ_DS) / g.parent_len) * g.parent_len;
-    const uint64_t off = ps - min((uint64_t)g.hist_limit, ps - g.vstart);
+    const uint64_t off = ps - min((uint64_t)g.hist_limit, ps - (SEG ? LZ_DS + rec->start : g.vstart));
     const int64_t lo = max((int64_t)q - (int64_t)g.max_dist, (int64_t)off);
     const uint32_t lit = g.buf[q];
     if (maxlen < g.min_run || (int64_t)q - (int64_t)g.min_dist < lo) return lit;
@@ -497,6 +532,12 @@ __device__ __noinline__ uint32_t lz_match_global(const LzGlob& g, uint64_t q) {
     }
     const uint32_t run = best >> 16;
     return run >= g.min_run ? (run << 16 | ((65535u - (best & 0xFFFFu)) - 1)) : lit;
+}
+__device__ __noinline__ uint32_t lz_match_global(const LzGlob& g, uint64_t q) {
+    return lz_match_global_at<false>(g, q, nullptr);
+}
+__device__ __noinline__ uint32_t lz_match_global_seg(const LzGlob& g, uint64_t q, const SegChunk* chunks) {
+    return lz_match_global_at<true>(g, q, chunks);
 }
 }  // namespace
 
@@ -534,15 +575,12 @@ __device__ __forceinline__ void dist_sym(uint32_t d, uint32_t& sym, uint32_t& ne
         ex = d & ((1u << ne) - 1);
     }
 }
-}  // namespace
-
-extern "C" __global__ void __launch_bounds__(DT, 1)
-ndfl_lz_encode_kernel(LzEncArgs a) {
-    __shared__ __attribute__((aligned(16))) uint32_t big[32768];   // steps (u16) -> scratch -> bit buffer
-    __shared__ uint32_t tokm[2048];                                 // token starts, 1 bit per position
-    __shared__ Persist ps;
-    __shared__ uint32_t hdrw[HDRW];                                 // the block header while `big` is zeroed
-    __shared__ uint32_t wexit[16];                                  // the parse walk's true exit per wave
+// One chunk (the kernels below).  SEG: the chunk's length, BFINAL and fallback geometry from its
+// record; its stream's first chunk publishes its prefix from the stream's own base in the staged
+// output and does not look back, so a later chunk's look-back ends inside its stream.
+template <bool SEG>
+__device__ __forceinline__ void lz_encode_chunk(const LzEncArgs& a, uint32_t* big, uint32_t* tokm, Persist& ps,
+                                                uint32_t* hdrw, uint32_t* wexit, const SegTab seg = SegTab{}) {
     static_assert(OUTW <= 32768, "bit buffer must fit the step array");
     uint32_t* obuf = big;
     HuffScr& scr = *(HuffScr*)big;
@@ -556,10 +594,16 @@ ndfl_lz_encode_kernel(LzEncArgs a) {
     if (tid == 0) ps.chunk = a.chunk_base + atomicAdd(a.ticket, 1u);
     for (int k = tid; k < 2048; k += DT) tokm[k] = 0;
     __syncthreads();
-    const uint32_t c = ps.chunk;
+    uint32_t c = ps.chunk;
+    if constexpr (SEG) c = (uint32_t)__builtin_amdgcn_readfirstlane((int)c);       // (its record: scalar loads)
     const uint64_t cs = (uint64_t)c * a.chunk_len;
-    const uint32_t len_c = (uint32_t)min((uint64_t)a.chunk_len, a.n - cs);
-    const bool is_final = a.final_last && (c + 1 == a.nchunks);
+    uint32_t segf = 0;
+    if constexpr (SEG) segf = seg.chunks[c].flags;
+    const uint32_t len_c = SEG ? seg.chunks[c].len : (uint32_t)min((uint64_t)a.chunk_len, a.n - cs);
+    const bool is_final = SEG ? (segf & SEG_LAST) != 0 : a.final_last && (c + 1 == a.nchunks);
+    const bool first = SEG && (segf & SEG_FIRST) != 0;
+    uint64_t base_bit = 0;
+    if constexpr (SEG) base_bit = 8 * seg.streams[seg.chunks[c].stream].obase;
     const uint32_t* mt = a.match + (cs - a.batch_x0);
 
     // ---- parse: steps in LDS, one wave walks them (D/comp/Lz77Huffman.java:68-130) -----------
@@ -592,7 +636,7 @@ ndfl_lz_encode_kernel(LzEncArgs a) {
     const uint32_t sg0 = min(wv * segw, lenc), sg1 = min(sg0 + segw, lenc);
     uint32_t nrep = 0;
     auto fallback = [&](uint32_t q) -> uint32_t {                   // (wave-uniform q) returns the step
-        const uint32_t m = lz_match_global(a.g, LZ_DS + cs + q);
+        const uint32_t m = SEG ? lz_match_global_seg(a.g, LZ_DS + cs + q, seg.chunks) : lz_match_global(a.g, LZ_DS + cs + q);
         if (lane == 0) a.match_rw[cs + q - a.batch_x0] = m;
         if (lane == 0) step[q] = (uint16_t)((m >> 16) ? (m >> 16) : 1u);
         nrep++;
@@ -734,8 +778,12 @@ ndfl_lz_encode_kernel(LzEncArgs a) {
     const uint32_t eobLen = ps.litCode[256] >> 16;
     const uint64_t S = (uint64_t)hdrBits + tokTotal + eobLen;
     if (tid == 0) {
-        if (c == 0) st_agent(&a.status[0], ST_PRE | (a.base_bit + S));
-        else st_agent(&a.status[c], ST_AGG | S);
+        if constexpr (SEG) {
+            st_agent(&a.status[c], first ? ST_PRE | (base_bit + S) : ST_AGG | S);
+        } else {
+            if (c == 0) st_agent(&a.status[0], ST_PRE | (a.base_bit + S));
+            else st_agent(&a.status[c], ST_AGG | S);
+        }
         if (a.chunk_bits) a.chunk_bits[c] = S;
     }
     const uint32_t nwl = (uint32_t)((S + 31) >> 5) + 1;
@@ -763,7 +811,8 @@ ndfl_lz_encode_kernel(LzEncArgs a) {
 #undef NDFL_FOR_TOKENS
     __syncthreads();
     const uint64_t tq4 = a.stats ? wall_clock64() : 0;
-    block_lookback(c, a.base_bit, S, a.status, ps);
+    if constexpr (SEG) block_lookback<true>(c, base_bit, S, a.status, ps, first);
+    else block_lookback(c, a.base_bit, S, a.status, ps);
     block_store(obuf, ps.P, S, c, a.out, a.edge_w, a.edge_v);
     if (a.stats && tid == 0) {
         const uint64_t tq5 = wall_clock64();
@@ -771,4 +820,24 @@ ndfl_lz_encode_kernel(LzEncArgs a) {
         atomicAdd(&a.stats[11], tq4 - tq3); atomicAdd(&a.stats[12], tq5 - tq4); atomicAdd(&a.stats[13], 1ull);
     }
     (void)lane;
+}
+}  // namespace
+
+extern "C" __global__ void __launch_bounds__(DT, 1)
+ndfl_lz_encode_kernel(LzEncArgs a) {
+    __shared__ __attribute__((aligned(16))) uint32_t big[32768];   // steps (u16) -> scratch -> bit buffer
+    __shared__ uint32_t tokm[2048];                                 // token starts, 1 bit per position
+    __shared__ Persist ps;
+    __shared__ uint32_t hdrw[HDRW];                                 // the block header while `big` is zeroed
+    __shared__ uint32_t wexit[16];                                  // the parse walk's true exit per wave
+    lz_encode_chunk<false>(a, big, tokm, ps, hdrw, wexit);
+}
+extern "C" __global__ void __launch_bounds__(DT, 1)
+ndfl_lz_encode_seg_kernel(LzEncArgs a, SegTab t) {
+    __shared__ __attribute__((aligned(16))) uint32_t big[32768];
+    __shared__ uint32_t tokm[2048];
+    __shared__ Persist ps;
+    __shared__ uint32_t hdrw[HDRW];
+    __shared__ uint32_t wexit[16];
+    lz_encode_chunk<true>(a, big, tokm, ps, hdrw, wexit, t);
 }

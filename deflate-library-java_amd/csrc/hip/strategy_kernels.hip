@@ -97,17 +97,13 @@ ndfl_assemble_kernel(AsmArgs a) {
 
 // ---- Adler-32 (java.util.zip.Adler32, the zlib container's checksum: D/ZlibOutputStream.java:22,
 // D/ZlibInputStream.java:25) -------------------------------------------------------------------
-// One 1024-thread workgroup per 64 KiB segment: S = sum of bytes, T = sum of (len - i) * byte_i
-// (i from 0), both mod 65521; the host folds the segments in order: b += len*a + T, a += S.
-extern "C" __global__ void __launch_bounds__(1024)
-ndfl_adler_segments_kernel(const uint8_t* in, uint64_t n, uint32_t* seg_st) {
-    __shared__ unsigned long long rs[16], rt[16];
-    const uint32_t seg = blockIdx.x;
-    const uint64_t s0 = (uint64_t)seg * 65536;
-    const uint32_t len = (uint32_t)min((uint64_t)65536, n - s0);
+// (S, T) of the `len` <= 65536 bytes at `seg`, by 1024 threads (rs, rt: 16 words of LDS each), to st[0],
+// st[1]: S = sum of bytes, T = sum of (len - i) * byte_i (i from 0), both mod 65521.
+__device__ __forceinline__ void adler_segment(const uint8_t* seg, uint32_t len, unsigned long long* rs,
+                                              unsigned long long* rt, uint32_t* st) {
     const uint32_t t0 = threadIdx.x * 64;
     const uint32_t cnt = len > t0 ? min(64u, len - t0) : 0u;
-    const uint8_t* p = in + s0 + t0;
+    const uint8_t* p = seg + t0;
     uint32_t ss = 0, tt = 0;                         // sums over this thread's bytes, weights cnt - k
     if (cnt == 64 && (((uintptr_t)p) & 15) == 0) {
         const u32x4* q = (const u32x4*)p;
@@ -135,7 +131,18 @@ ndfl_adler_segments_kernel(const uint8_t* in, uint64_t n, uint32_t* seg_st) {
     if (threadIdx.x == 0) {
         unsigned long long a = 0, b = 0;
         for (int k = 0; k < 16; k++) { a += rs[k]; b += rt[k]; }
-        seg_st[2 * seg] = (uint32_t)(a % 65521u);
-        seg_st[2 * seg + 1] = (uint32_t)(b % 65521u);
+        st[0] = (uint32_t)(a % 65521u);
+        st[1] = (uint32_t)(b % 65521u);
     }
+}
+
+// One 1024-thread workgroup per 64 KiB segment; the host folds the segments in order: b += len*a + T,
+// a += S.
+extern "C" __global__ void __launch_bounds__(1024)
+ndfl_adler_segments_kernel(const uint8_t* in, uint64_t n, uint32_t* seg_st) {
+    __shared__ unsigned long long rs[16], rt[16];
+    const uint32_t seg = blockIdx.x;
+    const uint64_t s0 = (uint64_t)seg * 65536;
+    const uint32_t len = (uint32_t)min((uint64_t)65536, n - s0);
+    adler_segment(in + s0, len, rs, rt, seg_st + 2 * seg);
 }

@@ -460,6 +460,15 @@ class Context:
                                in_addr, in_size, out_addr, out_size, items, int(dynamic), min_run, max_run, min_dist,
                                max_dist, chunk_len, hist_limit, flags)
 
+    def deflate_batch_chunked_raw(self, in_addr, in_size, out_addr, out_size, items, dynamic, min_run, max_run, min_dist,
+                                  max_dist, chunk_len, hist_limit, flags):
+        """ndfl_deflate_batch_chunked: deflate_batch_lz77_raw with one workgroup per chunk instead of one wave
+        per stream (medium buffers); every valid tuple, the literal-only and the RLE form included; the
+        same items and the same (status, checksum, out_len, end_bits) per stream."""
+        return self._batch_raw("ndfl_deflate_batch_chunked", _lib.MemberItem, _lib.DeflateResult, self._DEFLATE_RESULT,
+                               in_addr, in_size, out_addr, out_size, items, int(dynamic), min_run, max_run, min_dist,
+                               max_dist, chunk_len, hist_limit, flags)
+
     def deflate_batch_multi_raw(self, in_addr, in_size, out_addr, out_size, items, subs, chunk_len, hist_limit, flags):
         """ndfl_deflate_batch_multi: deflate_batch_raw with MultiStrategy(subs...) as the strategy, `subs` a
         sequence of Lz77Huffman / Uncompressed.SINGLETON (or ready-made _lib.StrategyDesc records); the
@@ -494,12 +503,27 @@ class Context:
             raise NdflError(_lib.E_UNSUPPORTED, "ndfl_deflate_batch_multi")
         return subs
 
-    def _deflate_packed(self, buffers, fmt, kind, headers, strategy, chunk_len, hist_limit):
+    @staticmethod
+    def _chunks_tuple(strategy):
+        """The Lz77Huffman that path="chunks" runs for `strategy` (an Lz77Huffman, or a preset's name or
+        id); Uncompressed, MultiStrategy and BinarySplit are not encoded by chunk workgroups."""
+        s = _strategy_id(strategy)
+        if isinstance(s, Lz77Huffman):
+            return s
+        if isinstance(s, int) and Strategy.LITERAL_STATIC.value <= s <= Strategy.FULL_DYNAMIC.value:
+            return getattr(Lz77Huffman, Strategy(s).name)
+        raise NdflError(_lib.E_UNSUPPORTED, "ndfl_deflate_batch_chunked")
+
+    def _deflate_packed(self, buffers, fmt, kind, headers, strategy, chunk_len, hist_limit, path="wave"):
         """One batch over host buffers: each region is its header's bytes (the caller's part of a
         container) followed by room for ndfl_deflate_bound(len) bytes and the trailer.  Returns one
         (bytes from the header on, end_bits, checksum) per buffer."""
         L = load()
+        if path not in ("wave", "chunks"):
+            raise ValueError('path: "wave" or "chunks"')
         buffers = [bytes(b) for b in buffers]
+        if path == "chunks":
+            strategy = self._chunks_tuple(strategy)
         subs = self._batch_subs(strategy)
         split = isinstance(strategy, BinarySplit)
         if split and not isinstance(strategy.substrategy, Lz77Huffman):
@@ -523,7 +547,11 @@ class Context:
         out = ctypes.create_string_buffer(max(1, out_off))
         for at, h in zip(regions, headers):
             ctypes.memmove(ctypes.addressof(out) + at, bytes(h), len(h))
-        if subs:
+        if path == "chunks":
+            res = self.deflate_batch_chunked_raw(ctypes.addressof(src), len(packed), ctypes.addressof(out), out_off, items,
+                                                 strategy.useDynamicHuffmanCodes, *strategy.params, chunk_len, hist_limit,
+                                                 0)
+        elif subs:
             res = self.deflate_batch_multi_raw(ctypes.addressof(src), len(packed), ctypes.addressof(out), out_off, items,
                                                subs, chunk_len, hist_limit, 0)
         elif split:
@@ -543,25 +571,32 @@ class Context:
             done.append((ctypes.string_at(ctypes.addressof(out) + at, len(h) + olen), end_bits, checksum))
         return done
 
-    def deflate_batch(self, buffers, strategy=Strategy.RLE_DYNAMIC, chunk_len=65536, hist_limit=32768, sum=None):
+    def deflate_batch(self, buffers, strategy=Strategy.RLE_DYNAMIC, chunk_len=65536, hist_limit=32768, sum=None,
+                      path="wave"):
         """Compress many independent host buffers in one call, each as deflate() compresses it alone
         (RLE_* / LITERAL_* presets by name or id through ndfl_deflate_batch; an Lz77Huffman instance, FULL_*
         among them, through ndfl_deflate_batch_lz77; Uncompressed.SINGLETON, or a MultiStrategy over a flat
         list of at most 8 Lz77Huffman / Uncompressed, through ndfl_deflate_batch_multi; a BinarySplit over an
         Lz77Huffman through ndfl_deflate_batch_binsplit; any other MultiStrategy or BinarySplit raises
         NdflError(E_UNSUPPORTED)).  Returns one (bytes, end_bits, checksum) per buffer; checksum is
-        the buffer's CRC-32 / Adler-32 with sum = SUM_CRC32 / SUM_ADLER32, else 0."""
+        the buffer's CRC-32 / Adler-32 with sum = SUM_CRC32 / SUM_ADLER32, else 0.
+        path="wave" (the default) is one wave per buffer, for many small buffers; path="chunks" sends a
+        preset's name or id or an Lz77Huffman through ndfl_deflate_batch_chunked, one workgroup per chunk,
+        for buffers of one to a few dozen chunks -- the same bytes -- and raises NdflError(E_UNSUPPORTED)
+        for Uncompressed, MultiStrategy and BinarySplit."""
         buffers = list(buffers)
         kind = _lib.SUM_NONE if sum is None else int(sum)
-        return self._deflate_packed(buffers, _lib.FMT_RAW, kind, [b""] * len(buffers), strategy, chunk_len, hist_limit)
+        return self._deflate_packed(buffers, _lib.FMT_RAW, kind, [b""] * len(buffers), strategy, chunk_len, hist_limit,
+                                    path)
 
     def deflate_members(self, buffers, format, meta=None, strategy=Strategy.RLE_DYNAMIC, chunk_len=65536,
-                        hist_limit=32768):
+                        hist_limit=32768, path="wave"):
         """Compress many independent host buffers into complete zlib (FMT_ZLIB) or gzip (FMT_GZIP)
         members in one call: what ZlibOutputStream / GzipOutputStream write for each buffer alone.  The
         header is `meta`'s (a ZlibMetadata / GzipMetadata; default ZlibMetadata.DEFAULT / GzipMetadata()),
         the trailer the kernel's; `strategy` as for deflate_batch (BinarySplit(Lz77Huffman, minBlockLen) through
-        ndfl_deflate_batch_binsplit among them).  Returns one bytes object per buffer."""
+        ndfl_deflate_batch_binsplit among them) and `path` as for deflate_batch.  Returns one bytes object per
+        buffer."""
         from .streams import GzipMetadata, ZlibMetadata
         buffers = list(buffers)
         fmt = int(format)
@@ -575,7 +610,7 @@ class Context:
         else:
             raise ValueError("format: FMT_ZLIB or FMT_GZIP")
         done = self._deflate_packed(buffers, fmt, _lib.SUM_NONE, [header] * len(buffers), strategy, chunk_len,
-                                    hist_limit)
+                                    hist_limit, path)
         return [d[0] for d in done]
 
     def inflate_range_raw(self, in_addr, in_len, start_bit, end_bit, out_addr, dict_len, out_cap, flags):

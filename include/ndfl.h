@@ -434,8 +434,8 @@ int ndfl_deflate_batch(ndfl_ctx* ctx, const uint8_t* in, uint64_t in_size, uint8
  * while the stream is a few KiB, 0.6 ms per KiB (1.7 MB/s) once its window is full, and up to 1,792 waves run
  * at once.  65,536 x 512 B take 5.8 to 7.3 ms in a batch and 27 to 33 s in a loop, 4,096 x 4 KiB 1.8 to 3.4 ms
  * and 1.8 to 2.2 s; 256 x 1 MiB take 625 to 808 ms in a batch and 133 to 162 ms in a loop: the batch loses
- * there.  So one buffer alone is faster here below about 2.5 KB, ten below about 8 KB each, a hundred below about
- * 80 KB, 256 below about 220 KB; larger buffers, which ndfl_deflate_chunks_lz77 searches with whole workgroups
+ * there (buffers of that size go through ndfl_deflate_batch_chunked, below).  So one buffer alone is faster here
+ * below about 2.5 KB, ten below about 8 KB each, a hundred below about 80 KB, 256 below about 220 KB; larger buffers, which ndfl_deflate_chunks_lz77 searches with whole workgroups
  * and the window in LDS, belong there whatever the count.  Against ndfl_deflate_batch's RLE_DYNAMIC the kernel
  * takes 2.5 to 7 times as long on these small buffers, and 4 KiB text buffers come out at 56 % of their size
  * instead of 99 %.
@@ -486,7 +486,8 @@ int ndfl_deflate_batch_lz77(ndfl_ctx* ctx, const uint8_t* in, uint64_t in_size, 
  * about 0.08 ms per stream plus 0.13 ms per KiB while the stream is a few KiB, 0.6 ms per KiB once its window is
  * full, and up to 1,792 waves run at once.  65,536 x 512 B take 6.0 to 7.5 ms in a batch and 53 to 65 s in a
  * loop, 4,096 x 4 KiB 1.9 to 3.5 ms and 3.7 to 4.3 s; 256 x 1 MiB take 619 to 824 ms in a batch and 268 to
- * 318 ms in a loop: the batch loses there.  So one buffer alone is faster here below about 6 KB (0.18 ms + 0.13 ms
+ * 318 ms in a loop: the batch loses there (for one Lz77Huffman alone, buffers of that size go through
+ * ndfl_deflate_batch_chunked, below).  So one buffer alone is faster here below about 6 KB (0.18 ms + 0.13 ms
  * per KiB against 1.0 ms), and with the full-window rate ten are below about 16 KB each, a hundred below about
  * 170 KB, 256 below about 430 KB (0.18 ms + 0.6 ms per KiB against n x 1.0 ms).  Against ndfl_deflate_batch_lz77's
  * FULL_DYNAMIC on the same buffers the kernel takes 5 to 11 % longer, and 512-byte text buffers come out at 92 %
@@ -549,7 +550,8 @@ int ndfl_deflate_batch_multi(ndfl_ctx* ctx, const uint8_t* in, uint64_t in_size,
  * window full; up to 1,792 waves run at once.  65,536 x 512 B take 5.7 to 6.0 ms in a batch and 37 s in a loop
  * (2,048 of them measured: 1.15 to 1.17 s), 4,096 x 4 KiB 4.9 to 8.0 ms and 7.6 to 8.7 s; 256 x 1 MiB take 1.81
  * to 2.36 s in a batch and 1.22 to 1.74 s in a loop: the batch loses there, as the LZ77 and MultiStrategy batches
- * do.  So one buffer alone is faster here below about 4 KB (at 4 KiB: 1.7 to 2.7 ms against 1.9 to 2.1 ms), and
+ * do (for an Lz77Huffman without the split, buffers of that size go through ndfl_deflate_batch_chunked, below).  So
+ * one buffer alone is faster here below about 4 KB (at 4 KiB: 1.7 to 2.7 ms against 1.9 to 2.1 ms), and
  * with the full-window rate, which overstates the batch below some tens of KiB, ten are below about 10 KB each, a
  * hundred below about 115 KB, 256 below about 470 KB (0.1 ms + 2.3 ms per KiB against n x (2.1 ms + 0.0046 ms per
  * KiB)).  Against ndfl_deflate_batch_lz77's
@@ -561,6 +563,62 @@ int ndfl_deflate_batch_binsplit(ndfl_ctx* ctx, const uint8_t* in, uint64_t in_si
                                 const ndfl_member_item* items, ndfl_deflate_result* results, uint32_t n,
                                 const ndfl_strategy_desc* sub, int32_t min_block_len,
                                 uint32_t chunk_len, uint32_t hist_limit, uint32_t flags);
+
+/*
+ * ndfl_deflate_batch_lz77 for MEDIUM buffers, one to a few dozen chunks each (64 KiB pages, column chunks,
+ * HTTP bodies, zip entries of 100 KiB to a few MiB): the chunks of all streams go through the chunk encoders of
+ * ndfl_deflate_chunks / ndfl_deflate_chunks_lz77, one 1024-thread workgroup per chunk, and the number of kernel
+ * launches and host waits does not depend on n (it grows with the staged bytes: one pair of LZ launches per
+ * 256 MiB of them).  Stream i is DeflaterOutputStream(out, chunk_len, hist_limit, Lz77Huffman(dynamic, min_run,
+ * max_run, min_dist, max_dist)): write all bytes, then finish().  Signature, items, results, formats, `sum`,
+ * trailers, NDFL_E_CAPACITY with the required size and the first out_cap bytes stored, the rule that no byte of
+ * `out` outside [out_off, out_off + min(out_len, out_cap)) of some stream is written (any alignment, regions
+ * that touch), NDFL_IN_DEVICE / NDFL_OUT_DEVICE, stream ordering, ndfl_ctx_last_kernel_ms (here: every launch from
+ * the first encoder pass to the finishing pass), n == 0, overlapping or repeated input regions and the argument errors
+ * and their order are ndfl_deflate_batch_lz77's, word for word; on any error nothing is written to `out` or
+ * `results`.
+ *   dynamic, min_run, max_run, min_dist, max_dist
+ *               every valid tuple is accepted.  The literal-only form (0, 0, 0, 0) and the RLE form
+ *               (3, 258, 1, 1) run on the RLE / LITERAL chunk encoders, every other tuple on the LZ77 ones.
+ *   chunk_len   1..65536 (0: NDFL_E_ARG; above 65536: NDFL_E_UNSUPPORTED)
+ *   hist_limit  0..32768, else NDFL_E_ARG
+ * More than 2^31 - 1 chunks in all (an empty buffer has one) is NDFL_E_UNSUPPORTED.
+ * A stream's DEFLATE bytes and end_bits are bit-identical to ndfl_deflate_chunks_lz77(ctx, NULL, 0, hist_limit,
+ * data_i, len_i, chunk_len, ..., 1, 0, ...).  Chunk 0 of a stream has no history; a chunk that starts at stream
+ * offset cs sees the min(hist_limit, cs) bytes before it, its own stream's and never a neighbour's, whatever lies
+ * next to it in `in` or in the staged copy; an empty buffer gives the one empty final block.  A stream's CRC-32 or
+ * Adler-32 is combined on the device from per-chunk partials taken in one pass over all chunks; a batch that asks
+ * for no checksum skips that pass.
+ * Memory the context owns, grown on first use: the staged input gives every stream a slot of
+ * max(1, ceil(in_len / chunk_len)) whole chunks, so it costs the SUM OF THE SLOTS, plus 4 bytes per staged byte
+ * (of at most 256 MiB at a time) for the LZ77 matches, and the staged output costs the sum of
+ * ndfl_deflate_bound(in_len, chunk_len) + 16 per stream.  A batch of many buffers far smaller than chunk_len
+ * pays a whole slot for each: it belongs in ndfl_deflate_batch_lz77, or needs a smaller chunk_len.
+ * NDFL_DEFLATE_FUSED and NDFL_LZ_SEARCH=chain have no effect on this call.
+ * Crossover (measured on one MI355X, a CRC-32 per buffer, device buffers, chunk_len 65536, DESIGN.md §4
+ * "Chunk-parallel batched deflate"; FULL_DYNAMIC on text .. mixed data, RLE_DYNAMIC on text .. runs):
+ *   4,096 x 4 KiB    FULL_DYNAMIC 43.6 to 53.3 ms here, 1.69 to 1.79 ms in ndfl_deflate_batch_lz77, 2.2 to 2.4 s in
+ *                    a loop of ndfl_deflate_chunks_lz77 calls; RLE_DYNAMIC 0.90 to 1.22 ms here, 0.50 to 0.56 ms
+ *                    in ndfl_deflate_batch, 0.7 to 0.9 s in a loop of ndfl_deflate_chunks calls: the wave batch
+ *                    wins (a 4 KiB buffer pays a 64 KiB slot here)
+ *   4,096 x 64 KiB   FULL_DYNAMIC 38.4 to 66.0 ms here, 171 to 249 ms and 2.5 to 3.6 s; RLE_DYNAMIC 1.24 to 1.71 ms
+ *                    here, 3.55 to 4.00 ms and 0.8 to 1.0 s: this call wins
+ *   256 x 1 MiB      FULL_DYNAMIC 24.0 to 43.8 ms here, 613 to 755 ms and 156 to 257 ms; RLE_DYNAMIC 1.25 to 1.66 ms
+ *                    here, 26.1 to 29.3 ms and 48.5 to 65.7 ms: this call wins
+ * Downwards: this call's time follows the staged bytes, the slots (4,096 slots of 64 KiB cost what 256 buffers of
+ * 1 MiB do, whatever the buffers hold), a wave batch's the longest streams; with chunk_len 65536 and a few thousand
+ * buffers the wave batch is faster below about 15 to 20 KB per buffer (both searches; interpolated linearly between
+ * the 4 KiB and the 64 KiB shape).  Upwards: no buffer count or size was found at which one
+ * ndfl_deflate_chunks_lz77 call per buffer is faster.  At 1 MiB a buffer costs 0.09 ms here against 0.6 to 1.0 ms
+ * in the loop, nearly all of it per-call cost; the rate here, 11 GB/s of text, is what ndfl_deflate_chunks_lz77
+ * reaches inside one large stream (1 GiB in about 108 ms), so larger buffers do not turn it round.  What bounds
+ * this call is the memory above; one buffer of many chunks alone goes through ndfl_deflate_chunks_lz77, which
+ * needs no slots and no second copy of the output.
+ */
+int ndfl_deflate_batch_chunked(ndfl_ctx* ctx, const uint8_t* in, uint64_t in_size, uint8_t* out, uint64_t out_size,
+                               const ndfl_member_item* items, ndfl_deflate_result* results, uint32_t n,
+                               int dynamic, int min_run, int max_run, int min_dist, int max_dist,
+                               uint32_t chunk_len, uint32_t hist_limit, uint32_t flags);
 
 /*
  * Decompress the block-aligned bit range [start_bit, end_bit) of one raw DEFLATE stream: one GPU's

@@ -39,7 +39,10 @@ call refuses halvings of an odd length, so the comparison needs buffer sizes tha
 chunk_len equal to the buffer size (65,536 for the 1 MiB shape: 16 full chunks); these two modes, and
 deflate-lz next to them in one run, use that chunk_len.  512-byte buffers are too short to split at 256
 (one search per stream); --data mixed (a quarter each of digits, the text, random bytes and 16-valued
-bytes) gives the larger ones something to split.
+bytes) gives the larger ones something to split.  Through the chunk encoders (--mode deflate-chunked:
+RLE_DYNAMIC, beside deflate and deflate-loop; --mode deflate-chunked-lz: FULL_DYNAMIC, beside deflate-lz and
+deflate-lz-loop): one ndfl_deflate_batch_chunked call, a workgroup per chunk, everything else the same;
+the lines carry the sibling modes' "bench".  The deflate modes have a fourth shape, 4,096 x 64 KiB.
 """
 import argparse
 import ctypes
@@ -55,7 +58,10 @@ import zlib
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(os.path.dirname(HERE), "deflate-library-java_amd", "python"))
 
-SHAPES = {"64Kx512B": (65536, 512), "4Kx4KiB": (4096, 4096), "256x1MiB": (256, 1 << 20)}
+SHAPES = {"64Kx512B": (65536, 512), "4Kx4KiB": (4096, 4096), "256x1MiB": (256, 1 << 20), "4Kx64KiB": (4096, 65536)}
+INFLATE_SHAPES = ("64Kx512B", "4Kx4KiB", "256x1MiB")
+DEFLATE_MODES = ("deflate", "deflate-loop", "deflate-lz", "deflate-lz-loop", "deflate-multi", "deflate-multi-loop",
+                 "deflate-binsplit", "deflate-binsplit-loop", "deflate-chunked", "deflate-chunked-lz")
 
 
 def make_streams(name, seed):
@@ -127,7 +133,8 @@ def deflate_modes(a, modes):
     deflate-multi-loop: ndfl_deflate_batch_multi and ndfl_deflate_chunks_multi with
     MultiStrategy(Uncompressed, FULL_STATIC, FULL_DYNAMIC), likewise.  --mode deflate-binsplit and
     deflate-binsplit-loop: ndfl_deflate_batch_binsplit and ndfl_deflate_chunks_binsplit with
-    BinarySplit(FULL_DYNAMIC, 256), likewise, with chunk_len = min(the buffer size, 65536) for every mode of
+    BinarySplit(FULL_DYNAMIC, 256), likewise; --mode deflate-chunked and deflate-chunked-lz:
+    ndfl_deflate_batch_chunked with the RLE_DYNAMIC tuple and with FULL_DYNAMIC; with chunk_len = min(the buffer size, 65536) for every mode of
     the run (the loop refuses halvings of an odd length).  Input and output are
     device-resident; every buffer and every output region starts 16-byte aligned, and a region holds
     ndfl_deflate_bound bytes, so the loop's encoder writes it in place.  The first pass decodes every
@@ -140,6 +147,7 @@ def deflate_modes(a, modes):
     flags = ndfl.IN_DEVICE | ndfl.OUT_DEVICE
     strategy = ndfl._lib.STRATEGIES["RLE_DYNAMIC"]
     full_dynamic = (1, 3, 258, 1, 32768)             # Lz77Huffman.FULL_DYNAMIC
+    rle_dynamic = (1, 3, 258, 1, 1)                  # Lz77Huffman.RLE_DYNAMIC
     D = ndfl._lib.StrategyDesc                       # MultiStrategy(Uncompressed, FULL_STATIC, FULL_DYNAMIC)
     t3 = (D * 3)(D(ndfl._lib.KIND_UNCOMPRESSED, 0, 0, 0, 0, 0), D(ndfl._lib.KIND_LZ77, 0, 3, 258, 1, 32768),
                  D(ndfl._lib.KIND_LZ77, 1, 3, 258, 1, 32768))
@@ -167,8 +175,9 @@ def deflate_modes(a, modes):
         pi, po = d_in.data_ptr(), d_out.data_ptr()
         for mode in modes:
             out_lens, sums = [0] * n, [0] * n
-            batch = mode in ("deflate", "deflate-lz", "deflate-multi", "deflate-binsplit")
-            lz = mode in ("deflate-lz", "deflate-lz-loop")
+            chunked = mode in ("deflate-chunked", "deflate-chunked-lz")
+            batch = chunked or mode in ("deflate", "deflate-lz", "deflate-multi", "deflate-binsplit")
+            lz = mode in ("deflate-lz", "deflate-lz-loop", "deflate-chunked-lz")
             multi = mode in ("deflate-multi", "deflate-multi-loop")
             split = mode in ("deflate-binsplit", "deflate-binsplit-loop")
             if batch:
@@ -178,7 +187,10 @@ def deflate_modes(a, modes):
 
             def once():
                 if batch:
-                    if split:
+                    if chunked:
+                        rc = L.ndfl_deflate_batch_chunked(ctx._h, pi, n * in_stride, po, n * cap, arr, res, n,
+                                                          *(full_dynamic if lz else rle_dynamic), chunk_len, hist_limit, flags)
+                    elif split:
                         rc = L.ndfl_deflate_batch_binsplit(ctx._h, pi, n * in_stride, po, n * cap, arr, res, n, ctypes.byref(fd),
                                                            min_block_len, chunk_len, hist_limit, flags)
                     elif multi:
@@ -253,20 +265,22 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", required=True,
                     help="comma-separated: loop, batch, members, batch+sum; or deflate, deflate-loop, deflate-lz, "
-                         "deflate-lz-loop, deflate-multi, deflate-multi-loop, deflate-binsplit, deflate-binsplit-loop")
+                         "deflate-lz-loop, deflate-multi, deflate-multi-loop, deflate-binsplit, deflate-binsplit-loop, "
+                         "deflate-chunked, deflate-chunked-lz")
     ap.add_argument("--data", choices=["text", "runs", "mixed"], default="text", help="deflate modes: the buffers' content")
     ap.add_argument("--buffers", type=int, default=0, help="deflate modes: only the first N buffers of each shape")
     ap.add_argument("--format", choices=["zlib", "gzip", "raw-crc"], default="zlib",
                     help="members / batch+sum: the container of each stream")
-    ap.add_argument("--shapes", default=",".join(SHAPES))
+    ap.add_argument("--shapes", default="", help="default: every shape of the modes (the deflate modes have 4Kx64KiB too)")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--label", default="")
     a = ap.parse_args()
-    if all(m in ("deflate", "deflate-loop", "deflate-lz", "deflate-lz-loop", "deflate-multi", "deflate-multi-loop",
-                 "deflate-binsplit", "deflate-binsplit-loop") for m in a.mode.split(",")):
+    if all(m in DEFLATE_MODES for m in a.mode.split(",")):
+        a.shapes = a.shapes or ",".join(SHAPES)
         return deflate_modes(a, a.mode.split(","))
+    a.shapes = a.shapes or ",".join(INFLATE_SHAPES)
     import torch
     import ndfl
     ctx = ndfl.Context(0)
