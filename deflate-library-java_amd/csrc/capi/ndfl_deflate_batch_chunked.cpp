@@ -66,7 +66,7 @@ static int seg_build_tables(const ndfl_member_item* items, uint32_t n, uint32_t 
 
 // The RLE / LITERAL presets over all chunks (chunks_rle's split pipeline, segmented).
 static int seg_launch_rle(ndfl_ctx* c, hipStream_t s, const SegTab tab, const uint8_t* slots, uint32_t nch, uint64_t staged,
-                          uint32_t chunk_len, uint32_t hist_limit, int rle, int dyn) {
+                          uint32_t chunk_len, uint32_t hist_limit, int rle, int dyn, uint32_t* two_walks) {
     HIPCHK(c->d_hist.ensure((size_t)nch * HREC * 4));
     HIPCHK(c->d_codes.ensure((size_t)nch * CREC * 4));
     const uint32_t ntile = (nch + SCAN_TILE - 1) / SCAN_TILE;
@@ -87,6 +87,8 @@ static int seg_launch_rle(ndfl_ctx* c, hipStream_t s, const SegTab tab, const ui
     a.hist_out = c->d_hist.as<uint32_t>(); a.codes = c->d_codes.as<uint32_t>(); a.chunk_off = d_offs;
     a.c0 = 0;
     a.pf_dist = c->knobs.deflate_pf ? 2u * (uint32_t)c->ncu : 0u;
+    a.onewalk = c->knobs.deflate_onewalk ? 1u : 0u;
+    a.two_walks = two_walks;
     hipLaunchKernelGGL(ndfl_deflate_hist_seg_kernel, dim3(nch), dim3(1024), 0, s, a, tab);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(ndfl_deflate_codes_seg_kernel, dim3(nch), dim3(64), 0, s, a, tab);
@@ -190,13 +192,17 @@ static int deflate_batch_chunked_run(ndfl_ctx* c, const uint8_t* in, uint8_t* ou
     HIPCHK(c->d_crc.ensure(2ull * nch * sizeof(uint32_t)));
     HIPCHK(c->d_crc1.ensure(std::max<size_t>(64, (size_t)n * sizeof(uint32_t))));
     const int preset = lz77_preset(t, dynamic);
+    ScopedBuf two_walks;                // NDFL_STATS: the emit pass's chunks that took two walks
+    if (c->knobs.stats && preset >= 0) HIPCHK(two_walks.ensure(64));
 
     auto launch = [&](hipStream_t q, uint8_t* d_out, const ndfl_member_item* d_items, ndfl_deflate_result* d_res,
                       uint32_t*) -> int {
         HIPCHK(hipMemsetAsync(c->d_status.p, 0, nch * sizeof(uint64_t), q));
+        if (two_walks.p) HIPCHK(hipMemsetAsync(two_walks.p, 0, 64, q));
         if (preset >= 0)
             TRY(seg_launch_rle(c, q, tab, slots, nch, T.staged, chunk_len, hist_limit,
-                               preset == NDFL_RLE_STATIC || preset == NDFL_RLE_DYNAMIC, dynamic != 0));
+                               preset == NDFL_RLE_STATIC || preset == NDFL_RLE_DYNAMIC, dynamic != 0,
+                               two_walks.as<uint32_t>()));
         else
             TRY(seg_launch_lz(c, q, tab, buf, nch, T.staged, chunk_len, hist_limit, t, dynamic != 0));
         const uint32_t ne = 2 * nch;
@@ -220,7 +226,13 @@ static int deflate_batch_chunked_run(ndfl_ctx* c, const uint8_t* in, uint8_t* ou
                            (const uint64_t*)c->d_status.p, tab, d_items, (const uint32_t*)d_sums, d_out, d_res);
         return NDFL_OK;
     };
-    return batch_status(batch_run(c->batch, s, c->ev0, c->ev1, out, items, results, n, flags, &c->last_ms, launch));
+    const int rc = batch_status(batch_run(c->batch, s, c->ev0, c->ev1, out, items, results, n, flags, &c->last_ms, launch));
+    if (two_walks.p && rc == NDFL_OK) {                     // (batch_run has waited for the launches)
+        uint32_t tw = 0;
+        HIPCHK(hipMemcpy(&tw, two_walks.p, 4, hipMemcpyDeviceToHost));
+        fprintf(stderr, "[ndfl] deflate emit: %u chunks, %u took two walks\n", nch, tw);
+    }
+    return rc;
 }
 
 extern "C" int ndfl_deflate_batch_chunked(ndfl_ctx* c, const uint8_t* in, uint64_t in_size, uint8_t* out, uint64_t out_size,

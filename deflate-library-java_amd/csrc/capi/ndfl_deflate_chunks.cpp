@@ -186,6 +186,13 @@ static int chunks_rle(Frame& f, int rle, int dyn, BlockOpts o) {
         d_total = c->d_off.as<uint64_t>() + nch;
     }
     a.c0 = 0;
+    a.onewalk = c->knobs.deflate_onewalk ? 1u : 0u;
+    ScopedBuf two_walks;                // NDFL_STATS: the emit pass's chunks that took two walks
+    if (c->knobs.stats && split) {
+        HIPCHK(two_walks.ensure(64));
+        HIPCHK(hipMemsetAsync(two_walks.p, 0, 64, s));
+    }
+    a.two_walks = two_walks.as<uint32_t>();
     TRY(f.start_timing());
     if (split) {
         hipLaunchKernelGGL(ndfl_deflate_hist_kernel, dim3(nch), dim3(1024), 0, s, a);
@@ -215,6 +222,11 @@ static int chunks_rle(Frame& f, int rle, int dyn, BlockOpts o) {
         HIPCHK(hipMemcpyAsync(c->h_pinned + 4, c->d_crc1.p, 4, hipMemcpyDeviceToHost, s));
     }
     TRY(f.read_end(split ? d_total : a.status + (nch - 1)));
+    if (two_walks.p) {
+        uint32_t tw = 0;
+        HIPCHK(hipMemcpy(&tw, two_walks.p, 4, hipMemcpyDeviceToHost));
+        fprintf(stderr, "[ndfl] deflate emit: %u chunks, %u took two walks\n", nch, tw);
+    }
     if (prof.p) {
         std::vector<uint64_t> h((size_t)nch * 8);
         HIPCHK(hipMemcpy(h.data(), prof.p, (size_t)nch * 64, hipMemcpyDeviceToHost));

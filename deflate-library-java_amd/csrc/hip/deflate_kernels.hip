@@ -18,6 +18,8 @@
 //   6. tokens are packed into a word-aligned LDS bit buffer with LDS atomicOr and streamed out
 //      with coalesced stores; the two boundary words of each chunk go to an edge list merged by
 //      ndfl_edge_fixup.
+// The split pipeline's emit pass does 5 and 6 in one walk over the tokens: codes into a slot per lane,
+// the lanes' bit counts from that, the slots compacted at the scanned offsets (NDFL_TOKEN_WALK below).
 // D/ = /root/reference/src/io/nayuki/deflate/
 #pragma once
 #include "huffman_build.hpp"
@@ -30,6 +32,14 @@ constexpr int NW = DT / 64;               // waves per workgroup
 constexpr int MAX_CHUNK = 65536;
 constexpr int OUTW = 18600;               // LDS bit-buffer words (>= 594,362 bits)
 static_assert(sizeof(HuffScr) <= OUTW * 4, "the code-construction scratch is laid over the bit buffer");
+// The emit pass's one walk: a lane's codes go to a slot of its own in the bit buffer first (64 bytes of
+// 9-bit literals fill it exactly), the slots interleaved word by word (BitPutSlot).
+constexpr uint32_t SLOTW = 18;
+using SlotPut = BitPutSlot<SLOTW, DT>;
+constexpr uint32_t SLOT_OVER = 1u << 20;  // scanned with the lanes' bit counts: a lane's codes passed its slot
+static_assert(DT * SLOTW <= OUTW, "the lanes' slots are laid over the bit buffer");
+static_assert(OUTW * 32 < SLOT_OVER && (uint64_t)DT * SLOT_OVER + OUTW * 32 < (1ull << 32),
+              "a chunk's token bits and the count of lanes past their slots share one 32-bit sum");
 
 constexpr uint64_t ST_AGG = 1ull << 62;
 constexpr uint64_t ST_PRE = 2ull << 62;
@@ -78,6 +88,8 @@ struct Args {
     uint32_t c0;              // split passes: first chunk of this launch (slab pipeline), grid = chunks
     uint32_t pf_dist;         // split passes: touch chunk c + pf_dist (the next wave of resident
                               // workgroups on this XCD) into L2 while chunk c is processed; 0: off
+    uint32_t onewalk;         // emit pass: one token walk into per-lane slots (NDFL_DEFLATE_ONEWALK=0: two walks)
+    uint32_t* two_walks;      // emit pass, optional (NDFL_STATS): counts the chunks that took two walks
 };
 
 // Split pipeline record layouts.
@@ -216,7 +228,7 @@ __device__ __forceinline__ void deflate_chunk(const Args& a, uint32_t* obuf, Per
     }
     __syncthreads();
     uint32_t c = ps.chunk;
-    if constexpr (SEG) c = a.c0 + blockIdx.x;                       // (the same value, in a scalar register)
+    if constexpr (SEG || MODE == MODE_EMIT) c = a.c0 + blockIdx.x;  // (the same value, in a scalar register)
     const uint64_t cs = (uint64_t)c * a.chunk_len;
     uint32_t segf = 0;
     if constexpr (SEG) segf = t.chunks[c].flags;
@@ -397,17 +409,21 @@ __device__ __forceinline__ void deflate_chunk(const Args& a, uint32_t* obuf, Per
         const uint32_t gw0_ = o4_ ? (o2_ ? a3_ : a2_) : (o2_ ? a1_ : a0_);                             \
         const uint32_t gw1_ = o4_ ? (o2_ ? b3_ : b2_) : (o2_ ? b1_ : b0_);                             \
         const bool anyL_ = __any(lg_ != 0);                                                            \
+        uint32_t gb_ = 0;                                                                              \
+        if (MODE == MODE_EMIT) { gb_ = t0 + 8u * (uint32_t)o_; asm volatile("" : "+v"(gb_)); }         \
         __VA_ARGS__                                                                                    \
     }
 #define NDFL_BYTE(j) ((((j) < 4 ? gw0_ : gw1_) >> (8 * ((j) & 3))) & 0xFFu)
 // 0 or all ones: byte j of the group is a literal
 #define NDFL_LMASK(j) ((uint32_t)((int32_t)(lm_ << (31 - (j))) >> 31))
-    // a run starting at group byte j: its value v, start gpos and end pend (next start)
+    // a run starting at group byte j: its value v, start gpos and end pend (next start).  The emit
+    // pass's group base gb_ is opaque, or t0 + j is kept in a register for each of the 8 bytes through
+    // its three walks (it then spills).
 #define NDFL_RUN_L(j, ...)                                                                             \
     if ((lg_ >> (j)) & 1) {                                                                            \
         const int i_ = 8 * o_ + (j);                                                                   \
         const uint32_t v = NDFL_BYTE(j);                                                               \
-        const uint32_t gpos = t0 + (uint32_t)i_;                                                       \
+        const uint32_t gpos = MODE == MODE_EMIT ? gb_ + (j) : t0 + (uint32_t)i_;                       \
         const uint64_t rest_ = i_ < 63 ? (F >> (i_ + 1)) : 0ull;                                       \
         const uint32_t pend = rest_ ? gpos + 1 + (uint32_t)__builtin_ctzll(rest_) : nextStart;         \
         __VA_ARGS__                                                                                    \
@@ -486,7 +502,85 @@ _Pragma("unroll")
     // ---- 5. token bits per lane, chunk size, decoupled look-back ------------------------------
     const uint32_t d0 = __builtin_amdgcn_readfirstlane(ps.distCode[0]);       // workgroup-uniform: SGPRs
     const uint32_t c285 = __builtin_amdgcn_readfirstlane(ps.litCode[285]);
-    uint32_t mybits = 0;
+    const uint32_t d0c = d0 & 0xFFFF, d0l = d0 >> 16;
+    const uint32_t m258 = (c285 & 0xFFFF) | (d0c << (c285 >> 16));
+    const uint32_t m258l = (c285 >> 16) + d0l;
+    // The token walk: this lane's codes into BP (a BitPut or a BitPutSlot).  One literal code per
+    // literal byte (LM), the tokens of a run at its first byte (LG); a group in which no lane of the
+    // wave starts a run (wave-uniform) joins two codes per put (<= 30 bits).  Codes are looked up 4
+    // bytes ahead (8 would spill: the bit buffer state, the chunk's 16 words and the lookups share
+    // 64 VGPRs).
+#define NDFL_TOKEN_WALK(BP)                                                                            \
+    NDFL_FOR_GROUPS_L({                                                                                \
+        uint32_t pf[4];                                                                                \
+_Pragma("unroll")                                                                                      \
+        for (int j = 0; j < 4; j++) pf[j] = ps.litCode[NDFL_BYTE(j)];                                  \
+        if (!anyL_) {                                                                                  \
+_Pragma("unroll")                                                                                      \
+            for (int j = 0; j < 8; j += 2) {                                                           \
+                const uint32_t e0 = pf[j & 3] & NDFL_LMASK(j);                                         \
+                const uint32_t e1 = pf[(j + 1) & 3] & NDFL_LMASK(j + 1);                               \
+                if (j < 4) { pf[j] = ps.litCode[NDFL_BYTE(j + 4)]; pf[j + 1] = ps.litCode[NDFL_BYTE(j + 5)]; } \
+                const uint32_t l0 = e0 >> 16;                                                          \
+                BP.put((e0 & 0xFFFF) | ((e1 & 0xFFFF) << l0), l0 + (e1 >> 16));                        \
+            }                                                                                          \
+            continue;                                                                                  \
+        }                                                                                              \
+_Pragma("unroll")                                                                                      \
+        for (int j = 0; j < 8; j++) {                                                                  \
+            const uint32_t lc = pf[j & 3];                                                             \
+            if (j < 4) pf[j] = ps.litCode[NDFL_BYTE(j + 4)];                                           \
+            const uint32_t e = lc & NDFL_LMASK(j);                                                     \
+            BP.put(e & 0xFFFF, e >> 16);                                                               \
+            NDFL_RUN_L(j, {                                                                            \
+                const uint32_t lead = lead_of(gpos, v);                                                \
+                const uint32_t R = pend - gpos - lead;                                                 \
+                const uint32_t n258 = R / 258, m = R % 258;                                            \
+                if (lead) BP.put(lc & 0xFFFF, lc >> 16);                                               \
+                for (uint32_t k = 0; k < n258; k++) BP.put(m258, m258l);                               \
+                if (m >= 3) {                                                                          \
+                    uint32_t sym, ne, ex; run_sym(m, sym, ne, ex);                                     \
+                    const uint32_t sc = ps.litCode[sym];                                               \
+                    BP.put(sc & 0xFFFF, sc >> 16);                                                     \
+                    BP.put(ex, ne);                                                                    \
+                    BP.put(d0c, d0l);                                                                  \
+                } else {                                                                               \
+                    for (uint32_t k = 0; k < m; k++) BP.put(lc & 0xFFFF, lc >> 16);                    \
+                }                                                                                      \
+            })                                                                                         \
+        }                                                                                              \
+    })                                                                                                 \
+    if (ce) {                               /* copies past the lane's last byte (same value) */        \
+        const uint32_t lc = ps.litCode[w[15] >> 24];                                                   \
+        BP.put(lc & 0xFFFF, lc >> 16);                                                                 \
+        if (ce > 1) BP.put(lc & 0xFFFF, lc >> 16);                                                     \
+    }                                                                                                  \
+    BP.flush();
+    // MODE_EMIT walks the tokens once: every lane packs its codes from bit 0 of a slot of its own
+    // (SLOTW words, word k at obuf[k * DT + tid], plain LDS stores) and has its bit count from that.  After
+    // the scan below the slots are compacted into the contiguous buffer.  A chunk in which some lane
+    // has more than a slot's bits (a lane stops storing there and keeps counting) takes the two
+    // walks of the one-kernel encoder instead: bit counts, then codes at their final place.  Such a
+    // chunk has then been walked three times, one more than before the slots; the statistics count it
+    // ("took two walks"; none of the benchmark corpus's 65,536 chunks does).  "Some
+    // lane" rides on the scan of the bit counts as a count above any chunk's token bits (a workgroup
+    // reduction of its own would take LDS the kernel does not have).
+    bool onewalk = false;
+    uint32_t mybits = 0, myoff = 0, tokTotal = 0;
+    if constexpr (MODE == MODE_EMIT) {
+        if (a.onewalk) {
+            SlotPut bs; bs.init(obuf);
+            NDFL_TOKEN_WALK(bs)
+            mybits = bs.bits();
+            myoff = block_excl_scan<uint32_t, NW>(mybits + (mybits > SLOTW * 32 ? SLOT_OVER : 0u), ps.scan32, tokTotal);
+            tokTotal = __builtin_amdgcn_readfirstlane(tokTotal);
+            onewalk = tokTotal < SLOT_OVER;
+        }
+        if (!onewalk && tid == 0 && a.two_walks) atomicAdd(a.two_walks, 1u);
+    }
+    const uint64_t tp3a = wall_clock64();
+    if (!onewalk) {
+    mybits = 0;
     NDFL_FOR_GROUPS_L({
         uint32_t pf[8];
 _Pragma("unroll")
@@ -515,9 +609,8 @@ _Pragma("unroll")
         }
     })
     if (ce) mybits += ce * (ps.litCode[w[15] >> 24] >> 16);
-    const uint64_t tp3a = wall_clock64();
-    uint32_t tokTotal;
-    const uint32_t myoff = block_excl_scan<uint32_t, NW>(mybits, ps.scan32, tokTotal);
+    myoff = block_excl_scan<uint32_t, NW>(mybits, ps.scan32, tokTotal);
+    }
     const uint64_t tp3b = wall_clock64();
     const uint32_t eobLen = __builtin_amdgcn_readfirstlane(ps.litCode[256] >> 16);
     const uint32_t hdrBits = __builtin_amdgcn_readfirstlane(ps.hdrBits);
@@ -532,72 +625,46 @@ _Pragma("unroll")
     const uint64_t tp4 = wall_clock64();
     // zero the bit buffer (scratch is dead from here on); one spare word for the final shift
     const uint32_t nwl = (uint32_t)((S + 31) >> 5) + 1;
-    __syncthreads();
-    {
-        // the header words (zero past hdrBits), kept or from the record, start the buffer
+    // the header words (zero past hdrBits), kept or from the record, start the buffer
+    auto zero_buffer = [&]() {
         const uint32_t* hdr = MODE == MODE_FUSED ? hdrw : a.codes + (uint64_t)c * CREC + CREC_HDR;
         const uint32_t hw = (hdrBits + 31) >> 5;
         for (uint32_t k = (uint32_t)tid; k < nwl; k += DT) obuf[k] = k < hw ? hdr[k] : 0u;
-    }
-    __syncthreads();
+    };
     const uint32_t bit0 = 0;
 
     // ---- 6. emit ------------------------------------------------------------------------------
-    if (tid == 0) put_end_of_block(obuf, bit0 + hdrBits + tokTotal, ps.litCode[256]);
-    {
-        BitPut bp; bp.init(obuf, bit0 + hdrBits + myoff);
-        const uint32_t d0c = d0 & 0xFFFF, d0l = d0 >> 16;
-        const uint32_t m258 = (c285 & 0xFFFF) | (d0c << (c285 >> 16));
-        const uint32_t m258l = (c285 >> 16) + d0l;
-        // one literal code per literal byte (LM), the tokens of a run at its first byte (LG); a group
-        // in which no lane of the wave starts a run (wave-uniform) joins two codes per put (<= 30 bits)
-        NDFL_FOR_GROUPS_L({
-            // codes looked up 4 bytes ahead (8 would spill: the bit buffer state, the chunk's 16
-            // words and the lookups share 64 VGPRs)
-            uint32_t pf[4];
-_Pragma("unroll")
-            for (int j = 0; j < 4; j++) pf[j] = ps.litCode[NDFL_BYTE(j)];
-            if (!anyL_) {
-_Pragma("unroll")
-                for (int j = 0; j < 8; j += 2) {
-                    const uint32_t e0 = pf[j & 3] & NDFL_LMASK(j);
-                    const uint32_t e1 = pf[(j + 1) & 3] & NDFL_LMASK(j + 1);
-                    if (j < 4) { pf[j] = ps.litCode[NDFL_BYTE(j + 4)]; pf[j + 1] = ps.litCode[NDFL_BYTE(j + 5)]; }
-                    const uint32_t l0 = e0 >> 16;
-                    bp.put((e0 & 0xFFFF) | ((e1 & 0xFFFF) << l0), l0 + (e1 >> 16));
-                }
-                continue;
-            }
-_Pragma("unroll")
-            for (int j = 0; j < 8; j++) {
-                const uint32_t lc = pf[j & 3];
-                if (j < 4) pf[j] = ps.litCode[NDFL_BYTE(j + 4)];
-                const uint32_t e = lc & NDFL_LMASK(j);
-                bp.put(e & 0xFFFF, e >> 16);
-                NDFL_RUN_L(j, {
-                    const uint32_t lead = lead_of(gpos, v);
-                    const uint32_t R = pend - gpos - lead;
-                    const uint32_t n258 = R / 258, m = R % 258;
-                    if (lead) bp.put(lc & 0xFFFF, lc >> 16);
-                    for (uint32_t k = 0; k < n258; k++) bp.put(m258, m258l);
-                    if (m >= 3) {
-                        uint32_t sym, ne, ex; run_sym(m, sym, ne, ex);
-                        const uint32_t sc = ps.litCode[sym];
-                        bp.put(sc & 0xFFFF, sc >> 16);
-                        bp.put(ex, ne);
-                        bp.put(d0c, d0l);
-                    } else {
-                        for (uint32_t k = 0; k < m; k++) bp.put(lc & 0xFFFF, lc >> 16);
-                    }
-                })
-            }
-        })
-        if (ce) {                               // copies past the lane's last byte (same value)
-            const uint32_t lc = ps.litCode[w[15] >> 24];
-            bp.put(lc & 0xFFFF, lc >> 16);
-            if (ce > 1) bp.put(lc & 0xFFFF, lc >> 16);
+    if (MODE == MODE_EMIT && onewalk) {
+        // One walk: the lane's slot words into registers (w[] is dead) before the buffer is zeroed
+        // over them, then ORed in at the lane's bit offset.  A lane's first and last destination
+        // word can hold its neighbours' bits too; the words between are its own.
+        const uint32_t nsw = (mybits + 31) >> 5;
+        uint32_t sw[SLOTW];
+#pragma unroll
+        for (uint32_t k = 0; k < SLOTW; k++) sw[k] = k < nsw ? obuf[SlotPut::word(k)] : 0u;
+        __syncthreads();
+        zero_buffer();
+        __syncthreads();
+        if (tid == 0) put_end_of_block(obuf, bit0 + hdrBits + tokTotal, ps.litCode[256]);
+        const uint32_t B = bit0 + hdrBits + myoff;
+        const uint32_t sh = B & 31;
+        uint32_t* dst = obuf + (B >> 5);
+        const uint32_t ndw = mybits ? (sh + mybits + 31) >> 5 : 0u;        // (<= SLOTW + 1)
+#pragma unroll
+        for (uint32_t k = 0; k <= SLOTW; k++) {
+            const uint32_t cur = k < SLOTW ? sw[k] : 0u;
+            const uint32_t prv = k ? sw[k - 1] : 0u;
+            const uint32_t v = sh ? (cur << sh) | (prv >> (32 - sh)) : cur;
+            if (k < ndw) atomicOr(&dst[k], v);      // (plain stores to the words between measured slower)
         }
-        bp.flush();
+    } else {
+        // two walks: the bit buffer's scratch is dead from here on
+        __syncthreads();
+        zero_buffer();
+        __syncthreads();
+        if (tid == 0) put_end_of_block(obuf, bit0 + hdrBits + tokTotal, ps.litCode[256]);
+        BitPut bp; bp.init(obuf, bit0 + hdrBits + myoff);
+        NDFL_TOKEN_WALK(bp)
     }
     __syncthreads();
 
@@ -651,6 +718,10 @@ ndfl_deflate_emit_kernel(Args a) {
     __shared__ __attribute__((aligned(16))) uint32_t obuf[OUTW];
     __shared__ Persist ps;
     deflate_chunk<MODE_EMIT>(a, obuf, ps);
+    // Built for 8 waves per SIMD, that is 64 VGPRs in granules of 8; the one walk needs 62.  The last
+    // one counts as used, so the kernel's recorded register count stays the launch bound's (the tests
+    // compare it with earlier builds' 64) and nothing is lost.
+    asm volatile("" ::: "v63");
 }
 extern "C" __global__ void __launch_bounds__(DT, 8)
 ndfl_deflate_emit_seg_kernel(Args a, SegTab t) {

@@ -43,6 +43,38 @@ struct BitPut {
     }
 };
 
+// BitPut into a slot of SLOTW words that only this thread writes, from the slot's bit 0: full words go
+// out with plain stores (the slot needs no zeroing, its last word's bits past the count are zero).  A
+// thread that passes the slot's end stops storing and keeps counting, so bits() is its bit count
+// whether or not its codes fit.  The NT threads' slots are interleaved: word k of thread t is word
+// k * NT + t of `buf`, which a wave reaches without a bank conflict whatever k its lanes are at, and
+// whose end is the same byte offset for every thread (no register for a slot's bounds).
+template <uint32_t SLOTW, uint32_t NT>
+struct BitPutSlot {
+    static_assert((NT & (NT - 1)) == 0, "a power of two");
+    uint32_t lo;
+    uint32_t nb;
+    uint32_t wb;         // byte offset in buf of the word being filled
+    char* buf;
+    static __device__ __forceinline__ uint32_t word(uint32_t k) { return k * NT + threadIdx.x; }
+    __device__ __forceinline__ void init(uint32_t* b) { buf = (char*)b; wb = threadIdx.x * 4; nb = 0; lo = 0; }
+    __device__ __forceinline__ void put(uint32_t v, uint32_t n) {     // v < 2^n, n <= 30
+        const uint32_t nb0 = nb;
+        lo |= v << nb0;
+        nb = nb0 + n;
+        if (nb >= 32) {
+            if (wb < SLOTW * NT * 4) *(uint32_t*)(buf + wb) = lo;
+            wb += NT * 4;
+            nb -= 32;
+            lo = v >> (32 - nb0);
+        }
+    }
+    __device__ __forceinline__ void flush() {
+        if (nb && wb < SLOTW * NT * 4) *(uint32_t*)(buf + wb) = lo;
+    }
+    __device__ __forceinline__ uint32_t bits() const { return wb / (NT * 4) * 32 + nb; }
+};
+
 constexpr uint32_t CL_EXTRA_BITS[3] = {2, 3, 7};
 constexpr uint8_t CL_ORDER[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
 

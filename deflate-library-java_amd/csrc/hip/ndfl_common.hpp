@@ -24,6 +24,8 @@ struct Knobs {
     bool deflate_profile = false;  // NDFL_DEFLATE_PROFILE: per-phase encoder clocks (one-kernel encoder); code
                                    //   construction is the one `codes` figure (huffman_build.hpp has no clocks)
     bool deflate_fused = false;  // NDFL_DEFLATE_FUSED: the one-kernel encoder instead of the split passes
+    bool deflate_onewalk = true; // NDFL_DEFLATE_ONEWALK=0: the emit pass walks each chunk's tokens twice (bit
+                                 //   counts, then codes) instead of once into per-lane slots
     bool lz_stats = false;       // NDFL_LZ_STATS
     bool lz_chain = false;       // NDFL_LZ_SEARCH=chain: the round-3 hash-chain LZ77 search
     int lz_lead = -1;            // NDFL_LZ_LEAD: parse-driven search lead-in (-1: default)
@@ -45,6 +47,7 @@ struct Knobs {
         count_w = (uint32_t)num("NDFL_COUNT_W", 0);
         deflate_pf = num("NDFL_DEFLATE_PF", 1) != 0; deflate_profile = on("NDFL_DEFLATE_PROFILE");
         deflate_fused = on("NDFL_DEFLATE_FUSED");
+        deflate_onewalk = num("NDFL_DEFLATE_ONEWALK", 1) != 0;
         lz_stats = on("NDFL_LZ_STATS");
         const char* se = getenv("NDFL_LZ_SEARCH");
         lz_chain = se && !strcmp(se, "chain");
@@ -58,10 +61,11 @@ struct Knobs {
     // the effective switches, one line (printed by ndfl_ctx_create when stats are on)
     void print(FILE* f) const {
         fprintf(f, "[ndfl] context knobs: stats=%d host_times=%d host_link=%d no_hdrrec=%d emit_fast=%d no_bt=%d "
-                   "no_alias=%d count_w=%u deflate_pf=%d deflate_profile=%d deflate_fused=%d lz_stats=%d "
+                   "no_alias=%d count_w=%u deflate_pf=%d deflate_profile=%d deflate_fused=%d deflate_onewalk=%d lz_stats=%d "
                    "lz_search=%s lz_lead=%d test_segflip=%d flat=%d flat_min=%u batch_waves=%u seg_slab=%llu\n",
                 (int)stats, (int)host_times, (int)host_link, (int)no_hdrrec, (int)emit_fast, (int)no_bt,
-                (int)no_alias, count_w, (int)deflate_pf, (int)deflate_profile, (int)deflate_fused, (int)lz_stats,
+                (int)no_alias, count_w, (int)deflate_pf, (int)deflate_profile, (int)deflate_fused,
+                (int)deflate_onewalk, (int)lz_stats,
                 lz_chain ? "chain" : "parse", lz_lead, (int)test_segflip, (int)flat, flat_min, batch_waves,
                 (unsigned long long)seg_slab);
     }
