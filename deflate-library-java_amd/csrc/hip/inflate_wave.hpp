@@ -1466,6 +1466,49 @@ __device__ __forceinline__ void wr_flush_exact(Wr& w, gu8* out) {
     w.acc = 0;
     w.an = 0;
 }
+// The same writer in select form (the fast emit kernel): the held words are a shift register -- the
+// newest in q2, the oldest of three in q0 -- so a completed word goes in with three selects on one
+// condition and no compare of hn, and the only branch left is the 16-byte store itself.  n <= 4, so
+// an stays below 8 and `an & 3` is the count left after a word went.
+__device__ __forceinline__ void wrs_lit(Wr& w, gu8* out, uint32_t val, uint32_t n) {
+    w.acc |= (uint64_t)val << (8 * w.an);
+    w.an += n;
+    const bool full = w.an >= 4;
+    const uint32_t word = (uint32_t)w.acc;
+    if (full && w.hn == 3) *(gu128*)(out + NDFL_OA(w.dst - 12)) = u32x4v{w.q0, w.q1, w.q2, word};
+    w.q0 = full ? w.q1 : w.q0;
+    w.q1 = full ? w.q2 : w.q1;
+    w.q2 = full ? word : w.q2;
+    w.hn = (w.hn + (full ? 1u : 0u)) & 3u;
+    w.acc = full ? w.acc >> 32 : w.acc;
+    w.an &= 3u;
+    w.dst += full ? 4u : 0u;
+}
+__device__ __forceinline__ void wrs_drain(Wr& w, gu8* out) {
+    if (w.hn) {
+        gu8* d = out + NDFL_OA(w.dst - 4 * w.hn);
+        if (w.hn == 1) *(gu32*)d = w.q2;
+        if (w.hn == 2) *(gu64*)d = (uint64_t)w.q1 | ((uint64_t)w.q2 << 32);
+        if (w.hn == 3) { *(gu64*)d = (uint64_t)w.q0 | ((uint64_t)w.q1 << 32); *(gu32*)(d + 8) = w.q2; }
+        w.hn = 0;
+    }
+}
+__device__ __forceinline__ void wrs_flush_word(Wr& w, gu8* out) {
+    wrs_drain(w, out);
+    if (w.an) {
+        *(gu32*)(out + NDFL_OA(w.dst)) = (uint32_t)w.acc;
+        w.dst += w.an;
+        w.acc = 0;
+        w.an = 0;
+    }
+}
+__device__ __forceinline__ void wrs_flush_exact(Wr& w, gu8* out) {
+    wrs_drain(w, out);
+    for (uint32_t k = 0; k < w.an; k++) out[NDFL_OA(w.dst + k)] = (uint8_t)(w.acc >> (8 * k));
+    w.dst += w.an;
+    w.acc = 0;
+    w.an = 0;
+}
 __device__ __forceinline__ uint64_t ld8(const gu8* p) { return *(const gu64*)p; }
 __device__ __forceinline__ uint32_t ld4(const gu8* p) { return *(const gu32*)p; }
 // out[dst, dst + len) = out[dst - dist, ...), byte-serial semantics; every source byte is final and
@@ -2389,6 +2432,11 @@ ndfl_inflate_emit_wave_kernel(const uint32_t* w, uint64_t nwords, uint64_t nbits
 #ifndef NDFL_EMITF_WAVES_PER_SIMD
 #define NDFL_EMITF_WAVES_PER_SIMD 4
 #endif
+// steps a lane stays in the token loop's literal run at most, while the lanes that left it wait for
+// their general step (measured: profiles/emit_litrun_ab.txt)
+#ifndef NDFL_EMITF_LITRUN_K
+#define NDFL_EMITF_LITRUN_K 8
+#endif
 extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NDFL_EMITF_WAVES_PER_SIMD)))
 ndfl_inflate_emit_fast_kernel(const uint32_t* w, uint64_t nwords, uint64_t nbits, const EmitChain* chains,
                               uint32_t* ticket, uint8_t* out, ChainRes* res, uint32_t* ref, uint32_t* pend,
@@ -2500,58 +2548,80 @@ ndfl_inflate_emit_fast_kernel(const uint32_t* w, uint64_t nwords, uint64_t nbits
             auto token_loop = [&](auto ph) {
                 using PH = decltype(ph);
                 while (live && pos < end) {
-                    Tok tk;
-                    if (PH::value && fast && esc4) {
-                        // escape-prefix literal block: up to 8 literals, to the first escape byte
-                        const uint32_t lo = (uint32_t)bb.buf, hi = (uint32_t)(bb.buf >> 32);
-                        const uint32_t t = min(min(esc_index(lo, hi, esc4), bb.nb >> 3), (end - pos + 7) >> 3);
-                        if (t) {
-                            uint32_t b[8];
+                    if (fast) {
+                        // literal run: up to NDFL_EMITF_LITRUN_K steps of nothing but the table read, the
+                        // advance, the append and the refill, while the primary entry is a literal (pair)
+                        // more than 20 bits before lim: no pair reaches the lane's end (an entry advances
+                        // at most LB bits) and the buffer stays ahead of the checked tail.  Inside, lastb
+                        // holds the last step's entry: the byte before dst0 + n is set once on the way out.
+#pragma unroll 1
+                        for (uint32_t k = 0; k < NDFL_EMITF_LITRUN_K; k++) {
+                            // (the four- and eight-literal steps check the lane's end themselves and run up
+                            // to lim; one of them may pass it)
+                            if (PH::value && bb.pos >= lim) break;
+                            if (PH::value && esc4) {
+                                // escape-prefix literal block: up to 8 literals, to the first escape byte
+                                const uint32_t lo = (uint32_t)bb.buf, hi = (uint32_t)(bb.buf >> 32);
+                                const uint32_t t = min(min(esc_index(lo, hi, esc4), bb.nb >> 3), (end - bb.pos + 7) >> 3);
+                                if (t) {
+                                    uint32_t b[8];
 #pragma unroll
-                            for (uint32_t i = 0; i < 8; i++)
-                                b[i] = (T.lit[(i < 4 ? lo >> (8 * i) : hi >> (8 * (i - 4))) & 0xFFu] >> 9) & 0xFFu;
-                            const uint32_t v0 = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
-                            const uint32_t v1 = b[4] | (b[5] << 8) | (b[6] << 16) | (b[7] << 24);
-                            const uint32_t n0 = min(t, 4u);
-                            wr_lit(wr, gout, n0 == 4 ? v0 : v0 & ((1u << (8 * n0)) - 1u), n0);
-                            if (t > 4) wr_lit(wr, gout, t == 8 ? v1 : v1 & ((1u << (8 * (t - 4))) - 1u), t - 4);
-                            n += t;
-                            lsp = true;
-                            lastb = t > 4 ? (v1 >> (8 * (t - 5))) & 0xFFu : (v0 >> (8 * (t - 1))) & 0xFFu;
-                            lastok = true;
-                            // (a 64-bit shift by 64 is undefined: the hardware shifts by 0)
-                            bb.buf = t < 8 ? bb.buf >> (8 * t) : 0ull;
-                            bb.nb -= 8 * t;
-                            bb.pos += 8 * t;
+                                    for (uint32_t i = 0; i < 8; i++)
+                                        b[i] = (T.lit[(i < 4 ? lo >> (8 * i) : hi >> (8 * (i - 4))) & 0xFFu] >> 9) & 0xFFu;
+                                    const uint32_t v0 = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
+                                    const uint32_t v1 = b[4] | (b[5] << 8) | (b[6] << 16) | (b[7] << 24);
+                                    const uint32_t n0 = min(t, 4u);
+                                    wrs_lit(wr, gout, n0 == 4 ? v0 : v0 & ((1u << (8 * n0)) - 1u), n0);
+                                    if (t > 4) wrs_lit(wr, gout, t == 8 ? v1 : v1 & ((1u << (8 * (t - 4))) - 1u), t - 4);
+                                    lastb = ((t > 4 ? (v1 >> (8 * (t - 5))) & 0xFFu : (v0 >> (8 * (t - 1))) & 0xFFu) << 9);
+                                    // (a 64-bit shift by 64 is undefined: the hardware shifts by 0)
+                                    bb.buf = t < 8 ? bb.buf >> (8 * t) : 0ull;
+                                    bb.nb -= 8 * t;
+                                    bb.pos += 8 * t;
+                                    bb_refill(bb, v);
+                                    continue;
+                                }
+                            }
+                            if (PH::value && !esc4 && bb.nb >= 34 && bb.pos + 24 < end) {
+                                // four 8-bit literal codes at once (independent table reads at 0, 8, 16, 24 bits;
+                                // the lane's end is a token boundary, so none of the four passes it)
+                                const uint32_t lo = (uint32_t)bb.buf, hi = (uint32_t)(bb.buf >> 32);
+                                const uint32_t e0 = T.lit[lo & ((1u << LB) - 1u)], e1 = T.lit[(lo >> 8) & ((1u << LB) - 1u)];
+                                const uint32_t e2 = T.lit[(lo >> 16) & ((1u << LB) - 1u)];
+                                const uint32_t e3 = T.lit[__builtin_amdgcn_alignbit(hi, lo, 24) & ((1u << LB) - 1u)];
+                                // a single literal of 8 bits: bit 31, advance 8, first length 8, no pair
+                                if (((e0 & 0x800001FFu) == 0x80000088u) && ((e1 & 0x800001FFu) == 0x80000088u) &&
+                                    ((e2 & 0x800001FFu) == 0x80000088u) && ((e3 & 0x800001FFu) == 0x80000088u)) {
+                                    wrs_lit(wr, gout, ((e0 >> 9) & 0xFFu) | (((e1 >> 9) & 0xFFu) << 8) | (((e2 >> 9) & 0xFFu) << 16) | (((e3 >> 9) & 0xFFu) << 24), 4);
+                                    lastb = e3;
+                                    bb_skip(bb, 32);
+                                    bb_refill(bb, v);
+                                    continue;
+                                }
+                            }
+                            // (one exit test: the table read at any buffer is harmless)
+                            const uint32_t e = T.lit[(uint32_t)bb.buf & ((1u << LB) - 1u)];
+                            if (!((e >> 31) && bb.pos + 2u * LB < lim)) break;
+                            // [3:0] the advance, [8] a pair, [24:9] its one or two bytes (a single's second is 0)
+                            wrs_lit(wr, gout, (e >> 9) & 0xFFFFu, 1u + ((e >> 8) & 1u));
+                            lastb = e;
+                            bb_skip(bb, e & 15);
                             bb_refill(bb, v);
-                            pos = bb.pos;
+                        }
+                        pos = bb.pos;
+                        const uint32_t nn = (uint32_t)(wr.dst - dst0) + wr.an;     // (the writer's position is the count)
+                        if (nn != n) {
+                            lsp = true;
+                            lastb = (lastb >> ((lastb >> 8) & 1u ? 17 : 9)) & 0xFFu;
+                            lastok = true;
+                            n = nn;
+                        }
+                        if (PH::value) {                // (a four- or eight-literal step may pass lim)
                             fast = pos < lim;
-                            continue;
+                            if (pos >= end) break;
                         }
                     }
-                    if (PH::value && fast && !esc4 && bb.nb >= 34 && pos + 24 < end) {
-                        // four 8-bit literal codes at once (independent table reads at 0, 8, 16, 24 bits;
-                        // the lane's end is a token boundary, so none of the four passes it)
-                        const uint32_t lo = (uint32_t)bb.buf, hi = (uint32_t)(bb.buf >> 32);
-                        const uint32_t e0 = T.lit[lo & ((1u << LB) - 1u)], e1 = T.lit[(lo >> 8) & ((1u << LB) - 1u)];
-                        const uint32_t e2 = T.lit[(lo >> 16) & ((1u << LB) - 1u)];
-                        const uint32_t e3 = T.lit[__builtin_amdgcn_alignbit(hi, lo, 24) & ((1u << LB) - 1u)];
-                        // a single literal of 8 bits: bit 31, advance 8, first length 8, no pair
-                        if (((e0 & 0x800001FFu) == 0x80000088u) && ((e1 & 0x800001FFu) == 0x80000088u) &&
-                            ((e2 & 0x800001FFu) == 0x80000088u) && ((e3 & 0x800001FFu) == 0x80000088u)) {
-                            const uint32_t b3 = (e3 >> 9) & 0xFFu;
-                            wr_lit(wr, gout, ((e0 >> 9) & 0xFFu) | (((e1 >> 9) & 0xFFu) << 8) | (((e2 >> 9) & 0xFFu) << 16) | (b3 << 24), 4);
-                            n += 4;
-                            lsp = true;
-                            lastb = b3;
-                            lastok = true;
-                            bb_skip(bb, 32);
-                            bb_refill(bb, v);
-                            pos = bb.pos;
-                            fast = pos < lim;
-                            continue;
-                        }
-                    }
+                    Tok tk;
                     if (fast) {
                         tok_bb<true>(bb, v, T, ed, tk, end);
                         pos = bb.pos;
@@ -2560,7 +2630,7 @@ ndfl_inflate_emit_fast_kernel(const uint32_t* w, uint64_t nwords, uint64_t nbits
                         tok<true>(v, pos, T, ed, end, nb, tk);
                     }
                     if (tk.kind == K_LIT) {
-                        wr_lit(wr, gout, tk.val, tk.n);
+                        wrs_lit(wr, gout, tk.val, tk.n);
                         n += tk.n;
                         lsp = true;
                         lastb = tk.val >> (tk.n == 2 ? 8 : 0);
@@ -2581,7 +2651,7 @@ ndfl_inflate_emit_fast_kernel(const uint32_t* w, uint64_t nwords, uint64_t nbits
                             defer = (__hip_atomic_load(&pend[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & mk) != 0;
                         }
                     }
-                    wr_flush_word(wr, gout);
+                    wrs_flush_word(wr, gout);
                     if (!defer && dist == 1 && !lastok) lastb = gout[dst - 1];
                     if (!defer) {
                         wr_copy(gout, dst, len, dist, lastb);
@@ -2608,7 +2678,7 @@ ndfl_inflate_emit_fast_kernel(const uint32_t* w, uint64_t nwords, uint64_t nbits
                 }
             };
             if (ph8) token_loop(std::true_type{}); else token_loop(std::false_type{});
-            wr_flush_exact(wr, gout);
+            wrs_flush_exact(wr, gout);
             // the count pass's record, checked: the lane's replay lands on the next
             // lane's segment start having produced exactly the bytes the record counts
             if (live && kind != T_ERR && (n != rcnt || pos != end)) { kind = T_ERR; rsn = R_INTERNAL; }
