@@ -8,6 +8,7 @@
 #include "../hip/deflate_seg.hip"
 #include "../hip/inflate_kernels.hip"
 #include "../hip/inflate_batch.hip"
+#include "../hip/inflate_bgzf.hip"
 #include "../hip/deflate_batch.hip"
 #include "../hip/deflate_batch_lz.hip"
 #include "../hip/deflate_batch_multi.hip"
@@ -91,6 +92,7 @@ struct ndfl_ctx {
     int ncu = 0;                    // the device's compute units (0: unknown)
     InflateScratch inf;
     BatchScratch batch;             // ndfl_inflate_batch: items / results / host-output staging
+    BgzfScratch bgzf;               // ndfl_inflate_bgzf: the candidate list, the member table
     BatchLzScratch batch_lz;        // ndfl_deflate_batch_lz77 / _multi: the waves' link rings and token lists
     uint32_t* h_pinned = nullptr;   // small pinned area for results
     Knobs knobs;                    // switches read once at ndfl_ctx_create (ndfl_common.hpp)
@@ -191,6 +193,7 @@ int ndfl_ctx_destroy(ndfl_ctx* c) {
     for (int k = 0; k < 16; k++) { c->d_mstreams[k].release(); c->d_mbits[k].release(); }
     c->inf.release();
     c->batch.release();
+    c->bgzf.release();
     c->batch_lz.release();
     if (c->h_pinned) hipHostFree(c->h_pinned);
     if (c->ev0) hipEventDestroy(c->ev0);
@@ -430,6 +433,28 @@ int ndfl_inflate_members(ndfl_ctx* c, const uint8_t* in, uint64_t in_size, uint8
                                                        c->d_tabs.as<uint32_t>() + 1024));
     if (r == NDFL_OK) batch_public_reasons(results, n);
     return r;
+}
+
+int ndfl_inflate_bgzf(ndfl_ctx* c, const uint8_t* in, uint64_t in_len, uint8_t* out, uint64_t out_cap,
+                      ndfl_bgzf_result* result, ndfl_bgzf_member* table, uint32_t table_cap, uint32_t flags) {
+    if (!c || !result || (!in && in_len) || (!out && out_cap) || (!table && table_cap)) return NDFL_E_ARG;
+    if (in_len > (8ull << 30)) return NDFL_E_UNSUPPORTED;       // (candidate indices are 32-bit)
+    HIPCHK(hipSetDevice(c->device));
+    BgzfOutcome o;
+    const int r = batch_status(inflate_bgzf_run(c->inf, c->batch, c->bgzf, ordered_stream(c), c->ev0, c->ev1, in, in_len,
+                                                out, out_cap, &o, table, table_cap, flags, &c->last_ms,
+                                                c->d_tabs.as<uint32_t>() + 1024));
+    if (r != NDFL_OK) return r;
+    ndfl_member_result one{};
+    one.status = o.status;
+    batch_public_reasons(&one, 1);
+    result->status = one.status;
+    result->error_symbol = one.error_symbol;
+    result->n_members = o.n_members;
+    result->bad_member = o.bad_member;
+    result->out_len = o.out_len;
+    result->consumed_bytes = o.consumed;
+    return result->status;
 }
 
 int ndfl_deflate_batch(ndfl_ctx* c, const uint8_t* in, uint64_t in_size, uint8_t* out, uint64_t out_size,

@@ -9,7 +9,7 @@
 
 // Switches of a context, read once from the environment when the context is created
 // (ndfl_ctx_create).  None is needed in production: they select the decoder's hand-over paths for
-// the tests (EMIT_FAST, NO_BT, NO_ALIAS, COUNT_W, FLAT, TEST_SEGFLIP, BATCH_WAVES, SEG_SLAB), statistics for profiling (STATS, HOST_TIMES,
+// the tests (EMIT_FAST, NO_BT, NO_ALIAS, COUNT_W, FLAT, TEST_SEGFLIP, BATCH_WAVES, BGZF_GRID, SEG_SLAB), statistics for profiling (STATS, HOST_TIMES,
 // LZ_STATS), and the few A/B alternatives still measured against the defaults.
 struct Knobs {
     bool stats = false;          // NDFL_STATS: per-pass counters and phase clocks to stderr
@@ -35,6 +35,8 @@ struct Knobs {
                                  //   before the emit pass (the emit-side check must fail the decode)
     uint32_t batch_waves = 0;    // NDFL_BATCH_WAVES: cap of ndfl_inflate_batch's / _members' / ndfl_deflate_batch's grid
                                  //   (0: automatic); the tests put many streams on one wave with it
+    uint32_t bgzf_grid = 0;      // NDFL_BGZF_GRID: cap of the grids of ndfl_inflate_bgzf's discovery and layout kernels
+                                 //   (0: their own, FIND_GRID / LIST_GRID); the tests make every workgroup stride with it
     uint64_t seg_slab = 256ull << 20;  // NDFL_SEG_SLAB: staged bytes per launch of ndfl_deflate_batch_chunked's LZ kernels
                                        //   (whole chunks, at least one); the tests make a batch take several with it
     void read() {
@@ -56,18 +58,19 @@ struct Knobs {
         flat = num("NDFL_FLAT", 1) != 0;
         flat_min = (uint32_t)num("NDFL_FLAT_MIN", 49152);
         { const int bw = num("NDFL_BATCH_WAVES", 0); batch_waves = bw > 0 ? (uint32_t)bw : 0u; }
+        { const int bg = num("NDFL_BGZF_GRID", 0); bgzf_grid = bg > 0 ? (uint32_t)bg : 0u; }
         { const char* e = getenv("NDFL_SEG_SLAB"); const long long v = e ? atoll(e) : 0; if (v > 0) seg_slab = (uint64_t)v; }
     }
     // the effective switches, one line (printed by ndfl_ctx_create when stats are on)
     void print(FILE* f) const {
         fprintf(f, "[ndfl] context knobs: stats=%d host_times=%d host_link=%d no_hdrrec=%d emit_fast=%d no_bt=%d "
                    "no_alias=%d count_w=%u deflate_pf=%d deflate_profile=%d deflate_fused=%d deflate_onewalk=%d lz_stats=%d "
-                   "lz_search=%s lz_lead=%d test_segflip=%d flat=%d flat_min=%u batch_waves=%u seg_slab=%llu\n",
+                   "lz_search=%s lz_lead=%d test_segflip=%d flat=%d flat_min=%u batch_waves=%u bgzf_grid=%u seg_slab=%llu\n",
                 (int)stats, (int)host_times, (int)host_link, (int)no_hdrrec, (int)emit_fast, (int)no_bt,
                 (int)no_alias, count_w, (int)deflate_pf, (int)deflate_profile, (int)deflate_fused,
                 (int)deflate_onewalk, (int)lz_stats,
                 lz_chain ? "chain" : "parse", lz_lead, (int)test_segflip, (int)flat, flat_min, batch_waves,
-                (unsigned long long)seg_slab);
+                bgzf_grid, (unsigned long long)seg_slab);
     }
 };
 

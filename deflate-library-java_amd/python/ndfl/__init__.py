@@ -436,6 +436,52 @@ class Context:
         return self._inflate_packed(self.inflate_members_raw, "ndfl_inflate_members", streams,
                                     [(f, kind) for f in fmts], out_caps)
 
+    def inflate_bgzf_raw(self, in_addr, in_len, out_addr, out_cap, flags, table_cap=0):
+        """ndfl_inflate_bgzf: a whole blocked gzip (BGZF) file, its members found on the device.  Returns
+        ((code, error_symbol, n_members, bad_member, out_len, consumed_bytes), table) with code = 0 /
+        Reason+1 of the first failing member / E_CAPACITY (out_len: the bytes required) and table the first
+        min(table_cap, n_members + 1) (in_off, out_off) entries; other negative codes raise."""
+        self._order()
+        res = _lib.BgzfResult()
+        tab = (_lib.BgzfMember * max(1, table_cap))()
+        r = load().ndfl_inflate_bgzf(self._h, in_addr, in_len, out_addr, out_cap, ctypes.byref(res),
+                                     tab if table_cap else None, table_cap, flags)
+        if r != _lib.E_CAPACITY:
+            check(r, "ndfl_inflate_bgzf")
+        n = min(table_cap, res.n_members + 1)
+        return ((res.status, res.error_symbol, res.n_members, res.bad_member, res.out_len, res.consumed_bytes),
+                [(t.in_off, t.out_off) for t in tab[:n]])
+
+    def inflate_bgzf(self, data, out_cap=None):
+        """Decode a blocked gzip (BGZF) file held in host bytes in one call.  Returns (reason|None, bytes,
+        consumed_bytes, n_members): on a Reason the bytes decoded AND stored before the first failing member's
+        error (a member stores no more than its ISIZE: its region ends where the next one's begins),
+        consumed_bytes = the offset just past the last member found (bytes after it are ignored).  Without
+        out_cap a sizing call (which trusts the members' ISIZE fields) comes first and the decode runs at
+        the exact size; with it a file that needs more raises NdflError(E_CAPACITY)."""
+        data = bytes(data)
+        src = ctypes.create_string_buffer(data, max(1, len(data)))
+        if out_cap is None:
+            out_cap = self.inflate_bgzf_raw(ctypes.addressof(src), len(data), None, 0, 0)[0][4]
+        out = ctypes.create_string_buffer(max(1, out_cap))
+        (code, sym, n, bad, olen, consumed), _ = self.inflate_bgzf_raw(ctypes.addressof(src), len(data),
+                                                                      ctypes.addressof(out), out_cap, 0)
+        check(code, "ndfl_inflate_bgzf")
+        if code:
+            # the failing member's region ends at the next table entry
+            table = self.inflate_bgzf_raw(ctypes.addressof(src), len(data), None, 0, 0, table_cap=bad + 2)[1]
+            olen = min(olen, table[bad + 1][1])
+        return (None if code == 0 else Reason(code - 1)), out.raw[:olen], consumed, n
+
+    def bgzf_index(self, data):
+        """The member table of a blocked gzip (BGZF) file in host bytes, without decoding it: one (in_off,
+        out_off) per member and a last entry (consumed_bytes, total output) -- from the members' BSIZE and
+        ISIZE fields, which it trusts."""
+        data = bytes(data)
+        src = ctypes.create_string_buffer(data, max(1, len(data)))
+        n = self.inflate_bgzf_raw(ctypes.addressof(src), len(data), None, 0, 0)[0][2]
+        return self.inflate_bgzf_raw(ctypes.addressof(src), len(data), None, 0, 0, table_cap=n + 1)[1]
+
     _DEFLATE_RESULT = ("status", "checksum", "out_len", "end_bits")
 
     def deflate_batch_raw(self, in_addr, in_size, out_addr, out_size, items, strategy, chunk_len, hist_limit, flags):
@@ -764,3 +810,4 @@ def decompress(data):
 from .streams import (DeflaterOutputStream, InflaterInputStream, GzipMetadata, GzipOutputStream,  # noqa: E402
                       GzipInputStream, ZlibMetadata, ZlibOutputStream, ZlibInputStream)
 from .plugin import BitOutputStream  # noqa: E402
+from . import bgzf  # noqa: E402

@@ -40,7 +40,7 @@ EXPORTS = ["ndfl_abi_version", "ndfl_error_string", "ndfl_ctx_create", "ndfl_ctx
            "ndfl_inflate", "ndfl_inflate_range", "ndfl_inflate_resolve", "ndfl_bits_shift", "ndfl_crc32", "ndfl_adler32",
            "ndfl_crc32_combine", "ndfl_decide", "ndfl_compress_to", "ndfl_decision_free", "ndfl_inflate_sync",
            "ndfl_inflate_tail", "ndfl_inflate_headers", "ndfl_inflate_tail_map", "ndfl_ctx_error_symbol",
-           "ndfl_inflate_batch", "ndfl_inflate_members", "ndfl_deflate_batch", "ndfl_deflate_batch_lz77",
+           "ndfl_inflate_batch", "ndfl_inflate_members", "ndfl_inflate_bgzf", "ndfl_deflate_batch", "ndfl_deflate_batch_lz77",
            "ndfl_deflate_batch_multi", "ndfl_deflate_batch_binsplit", "ndfl_deflate_batch_chunked"]
 
 # ndfl_inflate_members: NDFL_FMT_* (an item's container) and NDFL_SUM_* (a raw item's checksum)
@@ -92,6 +92,18 @@ class MemberResult(ctypes.Structure):
                 ("checksum", ctypes.c_uint32), ("header_len", ctypes.c_uint32)]
 
 
+class BgzfMember(ctypes.Structure):
+    """ndfl_bgzf_member (include/ndfl.h)."""
+    _fields_ = [("in_off", ctypes.c_uint64), ("out_off", ctypes.c_uint64)]
+
+
+class BgzfResult(ctypes.Structure):
+    """ndfl_bgzf_result (include/ndfl.h)."""
+    _fields_ = [("status", ctypes.c_int32), ("error_symbol", ctypes.c_int32),
+                ("n_members", ctypes.c_uint32), ("bad_member", ctypes.c_uint32),
+                ("out_len", ctypes.c_uint64), ("consumed_bytes", ctypes.c_uint64)]
+
+
 class DeflateResult(ctypes.Structure):
     """ndfl_deflate_result (include/ndfl.h)."""
     _fields_ = [("status", ctypes.c_int32), ("checksum", ctypes.c_uint32),
@@ -140,6 +152,11 @@ def load():
     if hasattr(L, "ndfl_inflate_members"):
         L.ndfl_inflate_members.argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(MemberItem),
                                            ctypes.POINTER(MemberResult), u32, u32]
+    # (and the blocked-gzip entry point: scripts/bench_batch.py --mode bgzf-hostwalk and bgzf-loop measure
+    # their baselines on the build before it)
+    if hasattr(L, "ndfl_inflate_bgzf"):
+        L.ndfl_inflate_bgzf.argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(BgzfResult), ctypes.POINTER(BgzfMember),
+                                        u32, u32]
     # (and the batched deflate: scripts/bench_batch.py --mode deflate-loop measures its baseline on the
     # build before it)
     if hasattr(L, "ndfl_deflate_batch"):

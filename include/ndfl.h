@@ -344,6 +344,63 @@ int ndfl_inflate_members(ndfl_ctx* ctx, const uint8_t* in, uint64_t in_size, uin
                          const ndfl_member_item* items, ndfl_member_result* results, uint32_t n, uint32_t flags);
 
 /*
+ * Decompress a blocked gzip file (BGZF: bgzip, BAM, tabix-indexed VCF / BED) in one call.  Such a file is
+ * a concatenation of gzip members of at most 64 KiB, each carrying its own length in a `BC` subfield of
+ * its extra field (BSIZE) and its output length in its trailer (ISIZE), so the members are found and
+ * the output laid out on the device without decoding a bit; ndfl_inflate_members' kernel then decodes
+ * them all in one launch.  The number of launches grows only with the logarithm of the file's size (the
+ * rounds that mark the chain), not with the number of members, and the host syncs twice: once for the
+ * sizes, once at the end.
+ *
+ * Member start: p is one when in[p, p + 3) = 1f 8b 08, FLG (in[p + 3]) has bit 2, the 12 fixed bytes and
+ *   all XLEN extra bytes lie inside in_len, the walk over the extra field's subfields (SI1, SI2, 2-byte
+ *   LEN, LEN bytes) meets SI1 = 66, SI2 = 67, LEN = 2 with its two bytes inside the field, and BSIZE + 1
+ *   >= 12 + XLEN + 8.  Nothing else of the header is looked at here: reserved flags, the OS byte, FNAME /
+ *   FCOMMENT and FHCRC are checked by the decode, in the reference's order, as that member's Reason.
+ * Chain:  member 0 is at byte 0 and member k + 1 at off[k] + BSIZE[k] + 1.  The chain ends at in_len or
+ *   at the first position that is not a member start; that position is consumed_bytes, and the bytes
+ *   after it are ignored, as ndfl_inflate ignores trailing bytes (a missing EOF marker is no error).
+ *   Byte 0 not a member start: n_members = 0, status 0, out_len 0, consumed_bytes 0.  A member whose
+ *   BSIZE runs past in_len gets the in_len - off[k] bytes there are and fails in the decode
+ *   (UNEXPECTED_END_OF_STREAM) like any truncated member.  Look-alike headers off the chain -- inside
+ *   a stored block, say -- are not members.
+ * Layout: ISIZE[k] is the little-endian u32 in the member's last 4 bytes; out_off[k] is the exclusive
+ *   64-bit sum of the ISIZEs and member k's region is ISIZE[k] bytes.  A total above out_cap returns
+ *   NDFL_E_CAPACITY with out_len = the total: nothing is decoded and no byte of `out` is written.  So
+ *   out = NULL, out_cap = 0 is the sizing and index call -- which TRUSTS the ISIZE fields: the size it
+ *   reports is what a well-formed file decodes to, and a file that lies fails in the decoding call.
+ *   table (host memory, may be NULL with table_cap = 0) receives min(table_cap, n_members + 1)
+ *   entries, in every case; entry n_members is (consumed_bytes, total).
+ * Decode: every member as an NDFL_FMT_GZIP item of ndfl_inflate_members, its dictionary empty.  A wrong
+ *   ISIZE, too small or too large, is therefore DECOMPRESSED_SIZE_MISMATCH, the checksum is tested
+ *   first, and a Reason wins over capacity.  (Bytes between a member's trailer and off + BSIZE + 1 are
+ *   ignored by the decode; the layout still reads ISIZE from the member's last 4 bytes, and a member
+ *   that decodes without a Reason to another length is DECOMPRESSED_SIZE_MISMATCH too.)
+ * Result: the failing member with the LOWEST index decides, whatever order the members were decoded
+ *   in.  On a Reason out_len = out_off[bad] + the bytes member `bad` decoded before the error, of which
+ *   the first min(that, ISIZE[bad]) are stored, as ndfl_inflate_batch stores min(out_len, out_cap): out
+ *   holds the file's bytes up to out_off[bad] + min(the member's out_len, ISIZE[bad]) -- with an ISIZE
+ *   that is too small out_len lies past that, in the next member's region.  The bytes from there to the
+ *   total are unspecified; no byte at or past the total is ever written.
+ * Returns result->status, or NDFL_E_ARG (null ctx / result, null buffers with a size), NDFL_E_UNSUPPORTED
+ * (in_len above 8 GiB), NDFL_E_DEVICE.  flags (NDFL_IN_DEVICE, NDFL_OUT_DEVICE, NDFL_IN_PADDED) and stream
+ * ordering as for ndfl_inflate_members.  ndfl_ctx_last_kernel_ms covers all the call's kernels; of
+ * ndfl_ctx_timings, [1] is the part up to the layout's end and [3] the decode with the reduction.
+ */
+typedef struct { uint64_t in_off, out_off; } ndfl_bgzf_member;
+typedef struct {
+    int32_t  status;          /* 0, Reason+1 of the FIRST failing member in file order, or NDFL_E_CAPACITY */
+    int32_t  error_symbol;    /* that member's, else -1 */
+    uint32_t n_members;       /* members on the chain from byte 0 */
+    uint32_t bad_member;      /* index of the failing member, else n_members */
+    uint64_t out_len;         /* status 0: total output; Reason: out_off[bad] + that member's out_len;
+                                 NDFL_E_CAPACITY: bytes required */
+    uint64_t consumed_bytes;  /* offset just past the last member of the chain */
+} ndfl_bgzf_result;
+int ndfl_inflate_bgzf(ndfl_ctx* ctx, const uint8_t* in, uint64_t in_len, uint8_t* out, uint64_t out_cap,
+                      ndfl_bgzf_result* result, ndfl_bgzf_member* table, uint32_t table_cap, uint32_t flags);
+
+/*
  * Compress n independent buffers in one call: one kernel launch and one host sync whatever n is
  * (ndfl_deflate_chunks costs about eight launches and a sync per buffer).  The encoder's counterpart of
  * ndfl_inflate_batch / ndfl_inflate_members, with their items read the other way round: item i's raw

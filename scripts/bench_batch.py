@@ -43,6 +43,9 @@ bytes) gives the larger ones something to split.  Through the chunk encoders (--
 RLE_DYNAMIC, beside deflate and deflate-loop; --mode deflate-chunked-lz: FULL_DYNAMIC, beside deflate-lz and
 deflate-lz-loop): one ndfl_deflate_batch_chunked call, a workgroup per chunk, everything else the same;
 the lines carry the sibling modes' "bench".  The deflate modes have a fourth shape, 4,096 x 64 KiB.
+
+Blocked gzip files (--mode bgzf | bgzf-hostwalk | bgzf-loop; see bgzf_modes): one ndfl_inflate_bgzf call
+against one ndfl_inflate_members call on items a host walk built, and against one call per member.
 """
 import argparse
 import ctypes
@@ -261,12 +264,132 @@ def deflate_modes(a, modes):
         del d_in, d_out, d_back
 
 
+BGZF_MODES = ("bgzf", "bgzf-hostwalk", "bgzf-loop")
+BGZF_SIZES = {"16MiB": 256, "256MiB": 4096, "1GiB": 16384}          # blocks of 65,280 bytes
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+
+
+def bgzf_modes(a, modes):
+    """A blocked gzip (BGZF) file of 65,280-byte blocks of the --data corpus (text | mixed), zlib level 6,
+    device-resident and padded, decoded into device memory three ways:
+      bgzf           one ndfl_inflate_bgzf call: the members found and laid out on the device.
+      bgzf-hostwalk  the members found by a walk over a HOST copy of the file (BSIZE, ISIZE), then one
+                     ndfl_inflate_members call on those items: the best a build without ndfl_inflate_bgzf
+                     can do.  The walk is timed with the call ("walk_ms" is its share); bringing a
+                     device-resident file to the host for it is not ("d2h_ms", measured once).
+      bgzf-loop      one ndfl_inflate_members call per member, each told only where it starts: the next
+                     start is consumed_bits / 8 of the one before.
+    The distinct blocks are the 4,096 buffers of shape 4Kx64KiB; larger files repeat them (members are
+    independent).  Lines are "bench": "bgzf"; bgzf's carry the event times of discovery with layout
+    ("layout_ms") and of the members kernel with the reduction ("decode_ms")."""
+    import numpy as np
+    import torch
+    import ndfl
+    ctx = ndfl.Context(0)
+    ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+    flags = ndfl.IN_DEVICE | ndfl.OUT_DEVICE | ndfl.IN_PADDED
+    L = ndfl._lib.load()
+    block = 65280
+    sizes = a.shapes.split(",") if a.shapes else list(BGZF_SIZES)
+    distinct = min(4096, max(BGZF_SIZES[s] for s in sizes))
+    datas = [d[:block] for d in make_buffers("4Kx64KiB", a.seed, a.data)[:distinct]]
+    members = []
+    for d in datas:
+        co = zlib.compressobj(6, zlib.DEFLATED, -15, 9)
+        body = co.compress(d) + co.flush()
+        n = 18 + len(body) + 8
+        members.append(b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0" + struct.pack("<H", n - 1) + body +
+                       struct.pack("<II", zlib.crc32(d), len(d)))
+    d_want = torch.frombuffer(bytearray(b"".join(datas)), dtype=torch.uint8).cuda()
+    for name in sizes:
+        nblocks = BGZF_SIZES[name]
+        file = b"".join(members[i % distinct] for i in range(nblocks)) + BGZF_EOF
+        total = nblocks * block
+        host = bytearray((len(file) + ndfl.IN_PAD_BYTES + 15) // 16 * 16)
+        host[:len(file)] = file
+        d_in = torch.frombuffer(host, dtype=torch.uint8).cuda()
+        d_out = torch.zeros(total, dtype=torch.uint8, device="cuda")
+        pi, po = d_in.data_ptr(), d_out.data_ptr()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        host_copy = bytes(d_in[:len(file)].cpu().numpy())
+        d2h_ms = (time.perf_counter() - t0) * 1e3
+        assert host_copy == file
+        for mode in modes:
+            extra = {}
+
+            def once():
+                if mode == "bgzf":
+                    res = ndfl._lib.BgzfResult()
+                    rc = L.ndfl_inflate_bgzf(ctx._h, pi, len(file), po, total, ctypes.byref(res), None, 0, flags)
+                    assert rc == 0 and res.n_members == nblocks + 1 and res.out_len == total, (rc, res.n_members)
+                    assert res.consumed_bytes == len(file)
+                    t = ctx.timings()
+                    extra.update(layout_ms=round(t["inflate_find"], 3), decode_ms=round(t["inflate_emit"], 3))
+                    return ctx.last_kernel_ms()
+                if mode == "bgzf-hostwalk":
+                    t0 = time.perf_counter()
+                    items, p, o = [], 0, 0
+                    while p < len(host_copy):
+                        mlen = (host_copy[p + 16] | host_copy[p + 17] << 8) + 1     # (BC is these files' first subfield)
+                        isize = int.from_bytes(host_copy[p + mlen - 4:p + mlen], "little")
+                        items.append((p, mlen, o, isize))
+                        p += mlen
+                        o += isize
+                    arr = np.zeros((len(items), 5), dtype=np.uint64)
+                    arr[:, :4] = items
+                    arr[:, 4] = ndfl._lib.FMT_GZIP                                  # format (low word), sum = 0
+                    res = (ndfl._lib.MemberResult * len(items))()
+                    extra["walk_ms"] = round((time.perf_counter() - t0) * 1e3, 3)
+                    rc = L.ndfl_inflate_members(ctx._h, pi, len(file), po, total,
+                                                arr.ctypes.data_as(ctypes.POINTER(ndfl._lib.MemberItem)), res, len(items), flags)
+                    assert rc == 0 and all(r.status == 0 for r in res), rc
+                    return ctx.last_kernel_ms()
+                p, o = 0, 0
+                item = (ndfl._lib.MemberItem * 1)()
+                res = (ndfl._lib.MemberResult * 1)()
+                while p < len(file):
+                    item[0] = ndfl._lib.MemberItem(p, min(65536, len(file) - p), o, min(65536, total - o), ndfl._lib.FMT_GZIP, 0)
+                    rc = L.ndfl_inflate_members(ctx._h, pi, len(file), po, total, item, res, 1, flags)
+                    assert rc == 0 and res[0].status == 0, (rc, res[0].status, p)
+                    p += res[0].consumed_bits // 8
+                    o += res[0].out_len
+                assert o == total
+                return None
+
+            times, kms = [], None
+            for it in range(a.warmup + a.reps):
+                d_out.zero_()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                kms = once()
+                torch.cuda.synchronize()
+                dt = (time.perf_counter() - t0) * 1e3
+                if it == 0:
+                    for k in range(0, nblocks, distinct):
+                        m = min(distinct, nblocks - k) * block
+                        assert torch.equal(d_out[k * block:k * block + m], d_want[:m]), "decoded bytes differ"
+                if it >= a.warmup:
+                    times.append(dt)
+            med = statistics.median(times)
+            line = {"bench": "bgzf", "label": a.label, "mode": mode, "data": a.data, "file": name, "members": nblocks + 1,
+                    "in_bytes": len(file), "out_bytes": total, "ms_median": round(med, 3),
+                    "ms_all": [round(t, 3) for t in times], "out_MBps": round(total / med / 1e3, 1), **extra}
+            if mode == "bgzf-hostwalk":
+                line["d2h_ms"] = round(d2h_ms, 3)
+            if kms is not None:
+                line["kernel_ms_last"] = round(kms, 3)
+            print(json.dumps(line), flush=True)
+        del d_in, d_out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", required=True,
                     help="comma-separated: loop, batch, members, batch+sum; or deflate, deflate-loop, deflate-lz, "
                          "deflate-lz-loop, deflate-multi, deflate-multi-loop, deflate-binsplit, deflate-binsplit-loop, "
-                         "deflate-chunked, deflate-chunked-lz")
+                         "deflate-chunked, deflate-chunked-lz; or bgzf, bgzf-hostwalk, bgzf-loop (--shapes: 16MiB, "
+                         "256MiB, 1GiB; --data text | mixed)")
     ap.add_argument("--data", choices=["text", "runs", "mixed"], default="text", help="deflate modes: the buffers' content")
     ap.add_argument("--buffers", type=int, default=0, help="deflate modes: only the first N buffers of each shape")
     ap.add_argument("--format", choices=["zlib", "gzip", "raw-crc"], default="zlib",
@@ -277,6 +400,8 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--label", default="")
     a = ap.parse_args()
+    if all(m in BGZF_MODES for m in a.mode.split(",")):
+        return bgzf_modes(a, a.mode.split(","))
     if all(m in DEFLATE_MODES for m in a.mode.split(",")):
         a.shapes = a.shapes or ",".join(SHAPES)
         return deflate_modes(a, a.mode.split(","))
