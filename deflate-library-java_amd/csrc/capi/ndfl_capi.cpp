@@ -9,6 +9,7 @@
 #include "../hip/inflate_kernels.hip"
 #include "../hip/inflate_batch.hip"
 #include "../hip/inflate_bgzf.hip"
+#include "../hip/deflate_bgzf.hip"
 #include "../hip/deflate_batch.hip"
 #include "../hip/deflate_batch_lz.hip"
 #include "../hip/deflate_batch_multi.hip"
@@ -88,6 +89,7 @@ struct ndfl_ctx {
     DevBuf d_hist, d_codes, d_off;  // split RLE/LITERAL pipeline: histograms, code records, offsets
     DevBuf d_lz, d_link, d_match;   // LZ77 path: staging [pad|hist|data], hash links, per-position matches
     DevBuf d_segtab;                // ndfl_deflate_batch_chunked: the chunk table, then the stream table
+    DevBuf d_bgzw;                  // ndfl_deflate_bgzf: the head, the member lengths, the tile sums, the items, the table
     DevBuf d_mdata, d_mstreams[16], d_mbits[16], d_masm;   // strategy composition
     int ncu = 0;                    // the device's compute units (0: unknown)
     InflateScratch inf;
@@ -188,7 +190,7 @@ int ndfl_ctx_destroy(ndfl_ctx* c) {
     hipStreamSynchronize(c->stream);
     DevBuf* bufs[] = {&c->d_in, &c->d_out, &c->d_status, &c->d_ticket, &c->d_edge_w, &c->d_edge_v,
                       &c->d_crc, &c->d_crc1, &c->d_tabs, &c->d_hostio, &c->d_lz, &c->d_link, &c->d_match,
-                      &c->d_mdata, &c->d_masm, &c->d_hist, &c->d_codes, &c->d_off, &c->d_segtab};
+                      &c->d_mdata, &c->d_masm, &c->d_hist, &c->d_codes, &c->d_off, &c->d_segtab, &c->d_bgzw};
     for (DevBuf* b : bufs) b->release();
     for (int k = 0; k < 16; k++) { c->d_mstreams[k].release(); c->d_mbits[k].release(); }
     c->inf.release();
@@ -406,6 +408,7 @@ static int deflate_batch_launch(ndfl_ctx* c, Launch& launch, const uint8_t* in, 
 }
 
 #include "ndfl_deflate_batch_chunked.cpp"
+#include "ndfl_deflate_bgzf.cpp"
 
 extern "C" {
 

@@ -10,6 +10,8 @@
 // of staged data, the look-back restarting at each stream's first chunk.  Then the checksum partials of
 // all chunks, their combination per stream, and the finishing pass (deflate_seg.hip); batch_run
 // (inflate_batch.hip) carries the items, the results and host output as for the wave batches.
+// seg_prepare and seg_encode are those stages up to the finishing pass; ndfl_deflate_bgzf
+// (ndfl_deflate_bgzf.cpp) runs them too, with tables of its own and its own last passes.
 
 // The tables of a batch.
 struct SegTables {
@@ -144,6 +146,60 @@ static int seg_launch_lz(ndfl_ctx* c, hipStream_t s, const SegTab tab, const uin
     return NDFL_OK;
 }
 
+// The context's buffers of a segmented run over nch chunks of n streams, grown to its sizes, and the staged
+// input's frame [LZ_DS zero bytes | the slots, `staged` bytes, not written here | 64 zero bytes]: *buf.
+static int seg_prepare(ndfl_ctx* c, hipStream_t s, uint32_t nch, uint32_t n, uint64_t staged, uint64_t out_bytes,
+                       uint8_t** buf) {
+    HIPCHK(c->d_lz.ensure(LZ_DS + staged + 64));
+    *buf = c->d_lz.as<uint8_t>();
+    HIPCHK(hipMemsetAsync(*buf, 0, LZ_DS, s));
+    HIPCHK(hipMemsetAsync(*buf + LZ_DS + staged, 0, 64, s));
+    HIPCHK(c->d_out.ensure(out_bytes));
+    HIPCHK(c->d_status.ensure(std::max<size_t>(8, nch * sizeof(uint64_t))));
+    HIPCHK(c->d_ticket.ensure(64));
+    HIPCHK(c->d_edge_w.ensure(2ull * nch * sizeof(uint64_t)));
+    HIPCHK(c->d_edge_v.ensure(2ull * nch * sizeof(uint32_t)));
+    HIPCHK(c->d_crc.ensure(2ull * nch * sizeof(uint32_t)));
+    HIPCHK(c->d_crc1.ensure(std::max<size_t>(64, (size_t)n * sizeof(uint32_t))));
+    return NDFL_OK;
+}
+
+// The launches of a segmented run on stream q, the slots filled and the tables on the device: the encoders
+// of the tuple over all chunks, the edge fix-up, and the streams' checksums into c->d_crc1 (zeros without
+// any_sum; d_items: the streams' lengths, on the device).  What is left is the pass that takes every stream
+// out of the staged output: its end is its last chunk's status word.
+static int seg_encode(ndfl_ctx* c, hipStream_t q, const SegTab tab, uint8_t* buf, uint32_t nch, uint64_t staged,
+                      uint32_t chunk_len, uint32_t hist_limit, const LzTuple& t, int dynamic, bool any_sum,
+                      const ndfl_member_item* d_items, uint32_t n, uint32_t* two_walks) {
+    uint8_t* slots = buf + LZ_DS;
+    const int preset = lz77_preset(t, dynamic);
+    HIPCHK(hipMemsetAsync(c->d_status.p, 0, nch * sizeof(uint64_t), q));
+    if (two_walks) HIPCHK(hipMemsetAsync(two_walks, 0, 64, q));
+    if (preset >= 0)
+        TRY(seg_launch_rle(c, q, tab, slots, nch, staged, chunk_len, hist_limit,
+                           preset == NDFL_RLE_STATIC || preset == NDFL_RLE_DYNAMIC, dynamic != 0, two_walks));
+    else
+        TRY(seg_launch_lz(c, q, tab, buf, nch, staged, chunk_len, hist_limit, t, dynamic != 0));
+    const uint32_t ne = 2 * nch;
+    hipLaunchKernelGGL(ndfl_edge_fixup_kernel, dim3((ne + 255) / 256), dim3(256), 0, q, (const uint64_t*)c->d_edge_w.p,
+                       (const uint32_t*)c->d_edge_v.p, ne, c->d_out.as<uint32_t>());
+    HIPCHK(hipGetLastError());
+    uint32_t* d_sums = c->d_crc1.as<uint32_t>();
+    if (any_sum) {
+        hipLaunchKernelGGL(ndfl_seg_sums_kernel, dim3(nch), dim3(1024), 0, q, (const uint8_t*)slots, chunk_len, tab,
+                           (const uint32_t*)c->d_tabs.as<uint32_t>(), (const uint32_t*)(c->d_tabs.as<uint32_t>() + 1024),
+                           c->d_crc.as<uint32_t>());
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(ndfl_seg_sums_combine_kernel, dim3((uint32_t)(((uint64_t)n * 64 + 255) / 256)), dim3(256), 0, q,
+                           (const uint32_t*)c->d_crc.p, chunk_len, tab, d_items, n,
+                           (const uint32_t*)(c->d_tabs.as<uint32_t>() + 1024 + 64 + 1024), d_sums);
+        HIPCHK(hipGetLastError());
+    } else {
+        HIPCHK(hipMemsetAsync(d_sums, 0, (size_t)n * sizeof(uint32_t), q));
+    }
+    return NDFL_OK;
+}
+
 // The call, its arguments checked: tables, staged input, then everything else between batch_run's events.
 static int deflate_batch_chunked_run(ndfl_ctx* c, const uint8_t* in, uint8_t* out, const ndfl_member_item* items,
                                      ndfl_deflate_result* results, uint32_t n, const LzTuple& t, int dynamic,
@@ -162,12 +218,9 @@ static int deflate_batch_chunked_run(ndfl_ctx* c, const uint8_t* in, uint8_t* ou
     tab.chunks = c->d_segtab.as<SegChunk>();
     tab.streams = (const SegStream*)((char*)c->d_segtab.p + chunks_b);
 
-    // staged input: [LZ_DS zero bytes | the slots | 64 zero bytes]
-    HIPCHK(c->d_lz.ensure(LZ_DS + T.staged + 64));
-    uint8_t* buf = c->d_lz.as<uint8_t>();
+    uint8_t* buf = nullptr;
+    TRY(seg_prepare(c, s, nch, n, T.staged, T.out_bytes, &buf));
     uint8_t* slots = buf + LZ_DS;
-    HIPCHK(hipMemsetAsync(buf, 0, LZ_DS, s));
-    HIPCHK(hipMemsetAsync(slots + T.staged, 0, 64, s));
     std::unique_ptr<uint8_t[]> pack;                        // host input, packed: alive until batch_run has waited
     if (flags & NDFL_IN_DEVICE) {
         hipLaunchKernelGGL(ndfl_seg_gather_kernel, dim3(nch), dim3(256), 0, s, in, slots, tab, chunk_len);
@@ -184,46 +237,15 @@ static int deflate_batch_chunked_run(ndfl_ctx* c, const uint8_t* in, uint8_t* ou
         HIPCHK(hipMemcpyAsync(slots, pack.get(), T.staged, hipMemcpyHostToDevice, s));
     }
 
-    HIPCHK(c->d_out.ensure(T.out_bytes));
-    HIPCHK(c->d_status.ensure(nch * sizeof(uint64_t)));
-    HIPCHK(c->d_ticket.ensure(64));
-    HIPCHK(c->d_edge_w.ensure(2ull * nch * sizeof(uint64_t)));
-    HIPCHK(c->d_edge_v.ensure(2ull * nch * sizeof(uint32_t)));
-    HIPCHK(c->d_crc.ensure(2ull * nch * sizeof(uint32_t)));
-    HIPCHK(c->d_crc1.ensure(std::max<size_t>(64, (size_t)n * sizeof(uint32_t))));
-    const int preset = lz77_preset(t, dynamic);
     ScopedBuf two_walks;                // NDFL_STATS: the emit pass's chunks that took two walks
-    if (c->knobs.stats && preset >= 0) HIPCHK(two_walks.ensure(64));
+    if (c->knobs.stats && lz77_preset(t, dynamic) >= 0) HIPCHK(two_walks.ensure(64));
 
     auto launch = [&](hipStream_t q, uint8_t* d_out, const ndfl_member_item* d_items, ndfl_deflate_result* d_res,
                       uint32_t*) -> int {
-        HIPCHK(hipMemsetAsync(c->d_status.p, 0, nch * sizeof(uint64_t), q));
-        if (two_walks.p) HIPCHK(hipMemsetAsync(two_walks.p, 0, 64, q));
-        if (preset >= 0)
-            TRY(seg_launch_rle(c, q, tab, slots, nch, T.staged, chunk_len, hist_limit,
-                               preset == NDFL_RLE_STATIC || preset == NDFL_RLE_DYNAMIC, dynamic != 0,
-                               two_walks.as<uint32_t>()));
-        else
-            TRY(seg_launch_lz(c, q, tab, buf, nch, T.staged, chunk_len, hist_limit, t, dynamic != 0));
-        const uint32_t ne = 2 * nch;
-        hipLaunchKernelGGL(ndfl_edge_fixup_kernel, dim3((ne + 255) / 256), dim3(256), 0, q, (const uint64_t*)c->d_edge_w.p,
-                           (const uint32_t*)c->d_edge_v.p, ne, c->d_out.as<uint32_t>());
-        HIPCHK(hipGetLastError());
-        uint32_t* d_sums = c->d_crc1.as<uint32_t>();
-        if (T.any_sum) {
-            hipLaunchKernelGGL(ndfl_seg_sums_kernel, dim3(nch), dim3(1024), 0, q, (const uint8_t*)slots, chunk_len, tab,
-                               (const uint32_t*)c->d_tabs.as<uint32_t>(), (const uint32_t*)(c->d_tabs.as<uint32_t>() + 1024),
-                               c->d_crc.as<uint32_t>());
-            HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(ndfl_seg_sums_combine_kernel, dim3((uint32_t)(((uint64_t)n * 64 + 255) / 256)), dim3(256), 0, q,
-                               (const uint32_t*)c->d_crc.p, chunk_len, tab, d_items, n,
-                               (const uint32_t*)(c->d_tabs.as<uint32_t>() + 1024 + 64 + 1024), d_sums);
-            HIPCHK(hipGetLastError());
-        } else {
-            HIPCHK(hipMemsetAsync(d_sums, 0, (size_t)n * sizeof(uint32_t), q));
-        }
+        TRY(seg_encode(c, q, tab, buf, nch, T.staged, chunk_len, hist_limit, t, dynamic, T.any_sum, d_items, n,
+                       two_walks.as<uint32_t>()));
         hipLaunchKernelGGL(ndfl_seg_finish_kernel, dim3(n), dim3(1024), 0, q, c->d_out.as<uint8_t>(),
-                           (const uint64_t*)c->d_status.p, tab, d_items, (const uint32_t*)d_sums, d_out, d_res);
+                           (const uint64_t*)c->d_status.p, tab, d_items, (const uint32_t*)c->d_crc1.p, d_out, d_res);
         return NDFL_OK;
     };
     const int rc = batch_status(batch_run(c->batch, s, c->ev0, c->ev1, out, items, results, n, flags, &c->last_ms, launch));

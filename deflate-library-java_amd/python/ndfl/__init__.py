@@ -482,6 +482,46 @@ class Context:
         n = self.inflate_bgzf_raw(ctypes.addressof(src), len(data), None, 0, 0)[0][2]
         return self.inflate_bgzf_raw(ctypes.addressof(src), len(data), None, 0, 0, table_cap=n + 1)[1]
 
+    def deflate_bgzf_raw(self, in_addr, in_len, out_addr, out_cap, strategy_tuple, block_len, flags, table_cap=0):
+        """ndfl_deflate_bgzf: `in_len` bytes as a blocked gzip (BGZF) file of one member per block_len bytes
+        and the closing empty member, each member MultiStrategy(Lz77Huffman(*strategy_tuple),
+        Uncompressed.SINGLETON) of its block; strategy_tuple = (dynamic, min_run, max_run, min_dist, max_dist).
+        Returns ((code, n_members, bad_member, n_stored, out_len), table) with code = 0 / E_CAPACITY (out_len:
+        the bytes required; out_addr = None, out_cap = 0 sizes the file) / E_UNSUPPORTED (a member above 65,536
+        bytes: bad_member; or block_len above 65536: all else 0) and table the first min(table_cap, n_members
+        + 1) (file offset, data offset) entries; other negative codes raise."""
+        self._order()
+        res = _lib.BgzfWriteResult()
+        tab = (_lib.BgzfMember * max(1, table_cap))()
+        dynamic, min_run, max_run, min_dist, max_dist = strategy_tuple
+        r = load().ndfl_deflate_bgzf(self._h, in_addr, in_len, out_addr, out_cap, ctypes.byref(res),
+                                     tab if table_cap else None, table_cap, int(dynamic), min_run, max_run, min_dist,
+                                     max_dist, block_len, flags)
+        if r not in (_lib.E_CAPACITY, _lib.E_UNSUPPORTED):
+            check(r, "ndfl_deflate_bgzf")
+        n = min(table_cap, res.n_members + 1) if res.n_members else 0
+        return (r, res.n_members, res.bad_member, res.n_stored, res.out_len), [(t.in_off, t.out_off) for t in tab[:n]]
+
+    def deflate_bgzf(self, data, block_len=65280, strategy=Lz77Huffman.FULL_DYNAMIC):
+        """`data` (host bytes) as a blocked gzip (BGZF) file in one call: (bytes, table), table = one (file
+        offset, data offset) per member, the closing empty one included, and a last entry (file length,
+        len(data)) -- what bgzf_index gives for the file.  `strategy` is the Lz77Huffman of
+        MultiStrategy(strategy, Uncompressed.SINGLETON).  ValueError when
+        a member would exceed 65,536 bytes (an incompressible block with block_len above 65505)."""
+        if not isinstance(strategy, Lz77Huffman):
+            raise TypeError("strategy: an Lz77Huffman")
+        tup = (strategy.useDynamicHuffmanCodes,) + tuple(strategy.params)
+        data = bytes(data)
+        src = ctypes.create_string_buffer(data, max(1, len(data)))
+        cap = load().ndfl_bgzf_bound(len(data), block_len) if 1 <= block_len <= 65536 else 0
+        out = ctypes.create_string_buffer(max(1, cap))
+        (code, n, bad, _, olen), table = self.deflate_bgzf_raw(ctypes.addressof(src), len(data), ctypes.addressof(out), cap,
+                                                               tup, block_len, 0, table_cap=len(data) // max(1, block_len) + 3)
+        if code == _lib.E_UNSUPPORTED and n:
+            raise ValueError(f"BGZF member {bad} of more than 65536 bytes; use a smaller block_len")
+        check(code, "ndfl_deflate_bgzf")
+        return out.raw[:olen], table
+
     _DEFLATE_RESULT = ("status", "checksum", "out_len", "end_bits")
 
     def deflate_batch_raw(self, in_addr, in_size, out_addr, out_size, items, strategy, chunk_len, hist_limit, flags):

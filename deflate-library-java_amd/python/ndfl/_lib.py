@@ -41,7 +41,8 @@ EXPORTS = ["ndfl_abi_version", "ndfl_error_string", "ndfl_ctx_create", "ndfl_ctx
            "ndfl_crc32_combine", "ndfl_decide", "ndfl_compress_to", "ndfl_decision_free", "ndfl_inflate_sync",
            "ndfl_inflate_tail", "ndfl_inflate_headers", "ndfl_inflate_tail_map", "ndfl_ctx_error_symbol",
            "ndfl_inflate_batch", "ndfl_inflate_members", "ndfl_inflate_bgzf", "ndfl_deflate_batch", "ndfl_deflate_batch_lz77",
-           "ndfl_deflate_batch_multi", "ndfl_deflate_batch_binsplit", "ndfl_deflate_batch_chunked"]
+           "ndfl_deflate_batch_multi", "ndfl_deflate_batch_binsplit", "ndfl_deflate_batch_chunked",
+           "ndfl_deflate_bgzf", "ndfl_bgzf_bound"]
 
 # ndfl_inflate_members: NDFL_FMT_* (an item's container) and NDFL_SUM_* (a raw item's checksum)
 FMT_RAW, FMT_ZLIB, FMT_GZIP = 0, 1, 2
@@ -102,6 +103,12 @@ class BgzfResult(ctypes.Structure):
     _fields_ = [("status", ctypes.c_int32), ("error_symbol", ctypes.c_int32),
                 ("n_members", ctypes.c_uint32), ("bad_member", ctypes.c_uint32),
                 ("out_len", ctypes.c_uint64), ("consumed_bytes", ctypes.c_uint64)]
+
+
+class BgzfWriteResult(ctypes.Structure):
+    """ndfl_bgzf_write_result (include/ndfl.h)."""
+    _fields_ = [("status", ctypes.c_int32), ("n_members", ctypes.c_uint32), ("bad_member", ctypes.c_uint32),
+                ("n_stored", ctypes.c_uint32), ("out_len", ctypes.c_uint64)]
 
 
 class DeflateResult(ctypes.Structure):
@@ -180,6 +187,12 @@ def load():
         L.ndfl_deflate_batch_chunked.argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(MemberItem),
                                                  ctypes.POINTER(DeflateResult), u32, i32, i32, i32, i32, i32, u32, u32,
                                                  u32]
+    # (scripts/bench_batch.py --mode bgzf-deflate-host measures its baseline on the build before this one)
+    if hasattr(L, "ndfl_deflate_bgzf"):
+        L.ndfl_deflate_bgzf.argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(BgzfWriteResult), ctypes.POINTER(BgzfMember),
+                                        u32, i32, i32, i32, i32, i32, u32, u32]
+        L.ndfl_bgzf_bound.restype = u64
+        L.ndfl_bgzf_bound.argtypes = [u64, u32]
     L.ndfl_inflate_range.argtypes = [vp, vp, u64, u64, u64, vp, u64, u64, ctypes.POINTER(u64), ctypes.POINTER(u64),
                                      u32]
     L.ndfl_inflate_resolve.argtypes = [vp, ctypes.POINTER(u64)]

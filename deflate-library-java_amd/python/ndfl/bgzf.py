@@ -2,9 +2,11 @@
 at most 64 KiB, each with its own length (BSIZE) in a `BC` extra subfield, closed by an empty member.
 
 decompress() is one ndfl_inflate_bgzf call (after its sizing call): the members are found and laid
-out on the GPU and decoded in one launch.  compress() cuts the data into blocks and compresses them in
-one deflate_members call; only BSIZE, which depends on the compressed length, is patched in on the
-host.
+out on the GPU and decoded in one launch.  compress() is one ndfl_deflate_bgzf call for the strategies
+that call takes -- a MultiStrategy of one Lz77Huffman and Uncompressed, the default among them: the blocks
+are compressed, sized and packed back to back on the GPU.  Any other strategy cuts the data into blocks
+on the host and compresses them in one deflate_members call; only BSIZE, which depends on the compressed
+length, is then patched in on the host.
 """
 import ctypes
 
@@ -28,15 +30,29 @@ def member_with_bsize(member):
     return member[:BSIZE_AT] + (n - 1).to_bytes(2, "little") + member[BSIZE_AT + 2:]
 
 
+def _device_tuple(strategy):
+    """The Lz77Huffman X when `strategy` is exactly MultiStrategy(X, Uncompressed.SINGLETON), what
+    ndfl_deflate_bgzf writes; else None."""
+    if isinstance(strategy, MultiStrategy) and len(strategy.substrategies) == 2:
+        x, u = strategy.substrategies
+        if isinstance(x, Lz77Huffman) and u is Uncompressed.SINGLETON:
+            return x
+    return None
+
+
 def compress(data, block_len=BLOCK_LEN, strategy=None, context=None):
     """`data` as a BGZF file: one member per block_len bytes, then the 28-byte EOF member (empty input:
-    the EOF member alone).  The default strategy takes the smaller of a FULL_DYNAMIC block and a stored one."""
+    the EOF member alone).  The default strategy takes the smaller of a FULL_DYNAMIC block and a stored one.
+    ValueError when a member would be longer than 65,536 bytes."""
     from .streams import GzipMetadata
     data = bytes(data)
     if not 1 <= block_len <= 65536:
         raise ValueError("block_len: 1..65536")
     if strategy is None:
         strategy = MultiStrategy(Lz77Huffman.FULL_DYNAMIC, Uncompressed.SINGLETON)
+    x = _device_tuple(strategy)
+    if x is not None:
+        return _ctx_default(context).deflate_bgzf(data, block_len, x)[0]
     blocks = [data[i:i + block_len] for i in range(0, len(data), block_len)]
     members = []
     if blocks:

@@ -678,6 +678,71 @@ int ndfl_deflate_batch_chunked(ndfl_ctx* ctx, const uint8_t* in, uint64_t in_siz
                                uint32_t chunk_len, uint32_t hist_limit, uint32_t flags);
 
 /*
+ * Compress a buffer to a blocked gzip file (BGZF: bgzip, BAM, tabix) in one call: the counterpart of
+ * ndfl_inflate_bgzf.  The input is cut into blocks of block_len bytes, every block becomes one gzip member with
+ * its own length in a `BC` subfield (BSIZE), the members lie back to back from out[0], and the 28-byte empty
+ * member closes the file.  The blocks run through ndfl_deflate_batch_chunked's encoders, one workgroup per
+ * block; three passes of this call's own then size the members, scan their lengths and pack them, all on the
+ * device.  The number of launches does not depend on the number of members (but for the LZ77 encoders' loop
+ * over slabs of staged data, as in ndfl_deflate_batch_chunked); with NDFL_OUT_DEVICE the host syncs once, else
+ * twice (the sizes, then the file's bytes).
+ *
+ * Blocks: member k holds in[k * block_len, min((k + 1) * block_len, in_len)).  block_len is 1..65536 (0:
+ *   NDFL_E_ARG; above: NDFL_E_UNSUPPORTED); the tuple is checked first, as ndfl_deflate_batch_chunked checks
+ *   it (an invalid one: NDFL_E_ARG).  Empty input gives the closing member alone.  in_len above 8 GiB, or more
+ *   than 2^31 - 2 blocks, is NDFL_E_UNSUPPORTED, before anything is allocated.
+ * Member: exactly what GzipOutputStream (D/GzipOutputStream.java) writes for that block alone with
+ *   GzipMetadata(operatingSystem = UNKNOWN, extraField = 'B' 'C' 02 00 <BSIZE>) and MultiStrategy(
+ *   Lz77Huffman(dynamic, min_run, max_run, min_dist, max_dist), Uncompressed.SINGLETON): the 18 header bytes
+ *   1f 8b 08 04 | MTIME 0 | XFL 0 | OS ff | XLEN 6 | 42 43 02 00 | BSIZE = the member's length - 1; the DEFLATE
+ *   data; CRC-32 and ISIZE.  The DEFLATE data is one chunk that starts at bit 0, where MultiStrategy
+ *   (D/comp/MultiStrategy.java:19-57: the first substrategy with the fewest bits) reduces to one rule: the
+ *   stored form (D/comp/Uncompressed.java:19-47: 8 * len + 40 * nblk bits at bit 0, nblk = max(1, ceil(len /
+ *   65535))) is taken if and only if it has FEWER bits than the tuple's single final block, whose bytes and
+ *   bit count are ndfl_deflate_batch_chunked's for that block; a tie goes to the tuple.
+ * Size: a member's length must fit BSIZE.  With block_len <= 65505 none can exceed 65,536 bytes (26 + 65505 +
+ *   5 stored); above that an incompressible block can, and the call then returns NDFL_E_UNSUPPORTED with
+ *   bad_member = the lowest such index; nothing of `out` is specified.
+ * Layout: member k starts where member k - 1 ends (a 64-bit exclusive scan on the device).  table (host
+ *   memory, may be NULL with table_cap = 0) receives min(table_cap, n_members + 1) entries (file offset, data
+ *   offset), the last one (out_len, in_len): exactly what ndfl_inflate_bgzf reports for the file written.
+ * Capacity: a file longer than out_cap returns NDFL_E_CAPACITY with out_len = its length, and no byte of `out`
+ *   is written (the pack pass reads the total on the device), so out = NULL, out_cap = 0 sizes the file.  In
+ *   every case no byte at or past out + out_len is written, at any byte alignment of `out`: whole aligned
+ *   words are stored as words, a member's first and last bytes that share a word with a neighbour as bytes.
+ * ndfl_bgzf_bound (host only, no context): every member in its stored form, 26 + len + 5 * nblk, plus 28; 0
+ *   for a block_len outside 1..65536.  An upper bound of every file the call can write, exact when every
+ *   member is stored.
+ * Returns result->status, or NDFL_E_ARG (null ctx / result, null buffers with a size, block_len 0, an invalid
+ * tuple), NDFL_E_UNSUPPORTED (block_len or in_len past the limits; *result is then all zero), NDFL_E_DEVICE.
+ * NDFL_IN_DEVICE, NDFL_OUT_DEVICE and stream ordering as for the other batch calls; ndfl_ctx_last_kernel_ms
+ * covers every launch from the tables to the pack.  Memory the context owns: the staged input (in_len), 4
+ * bytes per staged byte (of at most 256 MiB at a time) for LZ77 matches, and per block the staged output's
+ * ndfl_deflate_bound(block_len, block_len) + 16 and about 110 bytes of tables; a block_len of a few bytes pays
+ * some 1,200 bytes a member.
+ * Crossover (measured on one MI355X, blocks of 65,280 bytes, FULL_DYNAMIC against stored, DESIGN.md §4 "BGZF
+ * writer"; against the composition this call replaces, as of commit 6ff466b: the blocks through the wave batch
+ * ndfl_deflate_batch_multi, BSIZE patched and the members joined on the host, host bytes to host bytes):
+ *   16 MiB, 257 members     1.8 ms (text, runs) to 3.0 ms (mixed data) device to device, 3.9 to 5.4 ms host to host;
+ *                           the composition 50 to 91 ms
+ *   256 MiB, 4,097 members  24 to 43 ms device to device, 366 to 420 ms host to host (host copies, not kernels);
+ *                           the composition 1.43 to 1.55 s
+ * No shape was measured at which the composition is faster; the smallest input measured is 16 MiB.
+ */
+typedef struct {
+    int32_t  status;      /* 0, NDFL_E_CAPACITY, or NDFL_E_UNSUPPORTED (a member longer than 65,536 bytes) */
+    uint32_t n_members;   /* members of the file written, the closing empty member included */
+    uint32_t bad_member;  /* lowest index of a member longer than 65,536 bytes, else n_members */
+    uint32_t n_stored;    /* members written as stored blocks */
+    uint64_t out_len;     /* the file's length; with NDFL_E_CAPACITY: the bytes required */
+} ndfl_bgzf_write_result;
+int ndfl_deflate_bgzf(ndfl_ctx* ctx, const uint8_t* in, uint64_t in_len, uint8_t* out, uint64_t out_cap,
+                      ndfl_bgzf_write_result* result, ndfl_bgzf_member* table, uint32_t table_cap,
+                      int dynamic, int min_run, int max_run, int min_dist, int max_dist,
+                      uint32_t block_len, uint32_t flags);
+uint64_t ndfl_bgzf_bound(uint64_t in_len, uint32_t block_len);
+
+/*
  * Decompress the block-aligned bit range [start_bit, end_bit) of one raw DEFLATE stream: one GPU's
  * shard of a stream decoded across GPUs, or one batch of a stream read incrementally
  * (NDFL_IN_PARTIAL, end_bit UINT64_MAX: InflaterInputStream's bounded input buffer,

@@ -46,6 +46,8 @@ the lines carry the sibling modes' "bench".  The deflate modes have a fourth sha
 
 Blocked gzip files (--mode bgzf | bgzf-hostwalk | bgzf-loop; see bgzf_modes): one ndfl_inflate_bgzf call
 against one ndfl_inflate_members call on items a host walk built, and against one call per member.
+Writing them (--mode bgzf-deflate | bgzf-deflate-host; see bgzf_deflate_modes): one ndfl_deflate_bgzf call
+against the blocks through Context.deflate_members with the headers patched and the members joined on the host.
 """
 import argparse
 import ctypes
@@ -383,13 +385,95 @@ def bgzf_modes(a, modes):
         del d_in, d_out
 
 
+BGZF_DEFLATE_MODES = ("bgzf-deflate", "bgzf-deflate-host")
+
+
+def bgzf_deflate_modes(a, modes):
+    """The write side: the --data corpus (text | runs | mixed) in blocks of 65,280 bytes, the shapes of the
+    bgzf modes, as a blocked gzip (BGZF) file with MultiStrategy(FULL_DYNAMIC, Uncompressed) per member:
+      bgzf-deflate       one ndfl_deflate_bgzf call, device to device ("io": "device", into a buffer of
+                         ndfl_bgzf_bound bytes) and host to host ("io": "host", bytes in, bytes out:
+                         Context.deflate_bgzf).
+      bgzf-deflate-host  what a build without the call does, host to host: the data sliced into blocks,
+                         Context.deflate_members on the wave path, BSIZE patched into every member and the
+                         members joined on the host ("io": "host").
+    Lines are "bench": "bgzf-deflate".  The first file of every mode is read back with Python's gzip."""
+    import gzip
+    import torch
+    import ndfl
+    from ndfl import bgzf
+    ctx = ndfl.Context(0)
+    ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+    L = ndfl._lib.load()
+    block = 65280
+    x = ndfl.Lz77Huffman.FULL_DYNAMIC
+    tup = (1,) + tuple(x.params)
+    sizes = a.shapes.split(",") if a.shapes else list(BGZF_SIZES)
+    distinct = min(4096, max(BGZF_SIZES[s] for s in sizes))
+    datas = [d[:block] for d in make_buffers("4Kx64KiB", a.seed, a.data)[:distinct]]
+    for name in sizes:
+        nblocks = BGZF_SIZES[name]
+        data = b"".join(datas[i % distinct] for i in range(nblocks))
+        total = len(data)
+        for mode in modes:
+            for io in (("device", "host") if mode == "bgzf-deflate" else ("host",)):
+                state = {}
+                if io == "device":
+                    d_in = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda()
+                    cap = L.ndfl_bgzf_bound(total, block)
+                    d_out = torch.zeros(cap, dtype=torch.uint8, device="cuda")
+
+                def once():
+                    if io == "device":
+                        res = ndfl._lib.BgzfWriteResult()
+                        rc = L.ndfl_deflate_bgzf(ctx._h, d_in.data_ptr(), total, d_out.data_ptr(), cap, ctypes.byref(res), None, 0,
+                                                 *tup, block, ndfl.IN_DEVICE | ndfl.OUT_DEVICE)
+                        assert rc == 0 and res.n_members == nblocks + 1, (rc, res.n_members)
+                        state.update(out_len=res.out_len, n_stored=res.n_stored)
+                        return ctx.last_kernel_ms()
+                    if mode == "bgzf-deflate":
+                        state["file"] = ctx.deflate_bgzf(data, block, x)[0]
+                        return ctx.last_kernel_ms()
+                    blocks = [data[i:i + block] for i in range(0, total, block)]
+                    members = ctx.deflate_members(blocks, ndfl.FMT_GZIP,
+                                                  meta=ndfl.GzipMetadata(operatingSystem="UNKNOWN", extraField=bgzf.EXTRA),
+                                                  strategy=ndfl.MultiStrategy(x, ndfl.Uncompressed.SINGLETON))
+                    state["file"] = b"".join(bgzf.member_with_bsize(m) for m in members) + bgzf.EOF
+                    return ctx.last_kernel_ms()
+
+                times, kms = [], None
+                for it in range(a.warmup + a.reps):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    kms = once()
+                    torch.cuda.synchronize()
+                    dt = (time.perf_counter() - t0) * 1e3
+                    if it == 0:
+                        f = bytes(d_out[:state["out_len"]].cpu().numpy()) if io == "device" else state["file"]
+                        assert gzip.decompress(f) == data, "the file does not hold the data"
+                        state["out_len"] = len(f)
+                    if it >= a.warmup:
+                        times.append(dt)
+                med = statistics.median(times)
+                line = {"bench": "bgzf-deflate", "label": a.label, "mode": mode, "io": io, "data": a.data, "file": name,
+                        "members": nblocks + 1, "in_bytes": total, "out_bytes": state["out_len"], "ms_median": round(med, 3),
+                        "ms_all": [round(t, 3) for t in times], "in_MBps": round(total / med / 1e3, 1),
+                        "kernel_ms_last": round(kms, 3)}
+                if "n_stored" in state:
+                    line["n_stored"] = state["n_stored"]
+                print(json.dumps(line), flush=True)
+                if io == "device":
+                    del d_in, d_out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", required=True,
                     help="comma-separated: loop, batch, members, batch+sum; or deflate, deflate-loop, deflate-lz, "
                          "deflate-lz-loop, deflate-multi, deflate-multi-loop, deflate-binsplit, deflate-binsplit-loop, "
                          "deflate-chunked, deflate-chunked-lz; or bgzf, bgzf-hostwalk, bgzf-loop (--shapes: 16MiB, "
-                         "256MiB, 1GiB; --data text | mixed)")
+                         "256MiB, 1GiB; --data text | mixed); or bgzf-deflate, bgzf-deflate-host (the same shapes; "
+                         "--data text | runs | mixed)")
     ap.add_argument("--data", choices=["text", "runs", "mixed"], default="text", help="deflate modes: the buffers' content")
     ap.add_argument("--buffers", type=int, default=0, help="deflate modes: only the first N buffers of each shape")
     ap.add_argument("--format", choices=["zlib", "gzip", "raw-crc"], default="zlib",
@@ -402,6 +486,8 @@ def main():
     a = ap.parse_args()
     if all(m in BGZF_MODES for m in a.mode.split(",")):
         return bgzf_modes(a, a.mode.split(","))
+    if all(m in BGZF_DEFLATE_MODES for m in a.mode.split(",")):
+        return bgzf_deflate_modes(a, a.mode.split(","))
     if all(m in DEFLATE_MODES for m in a.mode.split(",")):
         a.shapes = a.shapes or ",".join(SHAPES)
         return deflate_modes(a, a.mode.split(","))
