@@ -7,6 +7,7 @@
 #include "../hip/strategy_kernels.hip"
 #include "../hip/deflate_seg.hip"
 #include "../hip/inflate_kernels.hip"
+#include "ndfl_inflate.cpp"
 #include "../hip/inflate_batch.hip"
 #include "../hip/inflate_bgzf.hip"
 #include "../hip/deflate_bgzf.hip"
@@ -27,21 +28,6 @@
 #include <new>
 
 namespace {
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t n) {
-        if (n <= cap) return hipSuccess;
-        if (p) { hipFree(p); p = nullptr; cap = 0; }
-        size_t want = n < 4096 ? 4096 : n;
-        hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    void release() { if (p) hipFree(p); p = nullptr; cap = 0; }
-    template <class T> T* as() const { return (T*)p; }
-};
 
 // A call's own temporary buffer: released on every return path.  (The context's members are plain
 // DevBufs, released by ndfl_ctx_destroy.)
@@ -327,12 +313,22 @@ static int public_reason(ndfl_ctx* c, int r) {
 
 int ndfl_ctx_error_symbol(ndfl_ctx* c) { return c ? c->err_sym : -1; }
 
+// One decode of a filled-in frame, its results to the caller.
+static int run_decode(ndfl_ctx* c, Decode& d, const uint8_t* in, uint64_t in_len, uint64_t* out_len, uint64_t* consumed_bits) {
+    d.last_ms = &c->last_ms;
+    const int r = d.run(in, in_len);
+    *out_len = d.out_len;
+    *consumed_bits = d.consumed_bits;
+    return public_reason(c, r);
+}
+
 int ndfl_inflate(ndfl_ctx* c, const uint8_t* in, uint64_t in_len, uint8_t* out, uint64_t out_cap,
                  uint64_t* out_len, uint64_t* consumed_bits, uint32_t flags) {
     if (!c || !out_len || !consumed_bits || (!in && in_len)) return NDFL_E_ARG;
     HIPCHK(hipSetDevice(c->device));
-    return public_reason(c, inflate_run(c->inf, ordered_stream(c), in, in_len, 0, inf::NONE, out, 0, out_cap, out_len,
-                                        consumed_bits, flags, false, &c->last_ms));
+    Decode d{c->inf, ordered_stream(c)};
+    d.out = out; d.out_cap = out_cap; d.flags = flags;
+    return run_decode(c, d, in, in_len, out_len, consumed_bits);
 }
 
 }  // extern "C"
@@ -393,8 +389,8 @@ static int deflate_batch_args(const uint8_t* in, uint64_t in_size, const uint8_t
     return NDFL_OK;
 }
 
-// A batch runner's return code as the C ABI's.
-static int batch_status(int r) { return !r ? NDFL_OK : r == -4 ? NDFL_E_DEVICE : NDFL_E_INTERNAL; }
+// A batch runner's (or inflate_headers') return code as the C ABI's: 0, the device error, else an internal one.
+static int batch_status(int r) { return !r ? NDFL_OK : r == NDFL_E_DEVICE ? r : NDFL_E_INTERNAL; }
 
 // How the four batched deflate calls end once their arguments are checked: the frame's arguments and the
 // checksum tables into the launcher, which holds what is the call's own already, and the run.
@@ -403,7 +399,7 @@ static int deflate_batch_launch(ndfl_ctx* c, Launch& launch, const uint8_t* in, 
                                 ndfl_deflate_result* results, uint32_t n, uint32_t chunk_len, uint32_t flags) {
     HIPCHK(hipSetDevice(c->device));
     launch.a.n = n; launch.a.chunk_len = chunk_len; launch.a.crc_tab = c->d_tabs.as<uint32_t>();
-    return batch_status(deflate_batch_run(c->batch, &c->d_in.p, &c->d_in.cap, ordered_stream(c), c->ev0, c->ev1, in, out,
+    return batch_status(deflate_batch_run(c->batch, c->d_in, ordered_stream(c), c->ev0, c->ev1, in, out,
                                           items, results, n, flags, launch, &c->last_ms));
 }
 
@@ -550,24 +546,27 @@ int ndfl_inflate_range(ndfl_ctx* c, const uint8_t* in, uint64_t in_len, uint64_t
     if (deferred && !(flags & NDFL_OUT_DEVICE)) return NDFL_E_ARG;
     if (partial && (deferred || end_bit != UINT64_MAX)) return NDFL_E_ARG;
     HIPCHK(hipSetDevice(c->device));
-    return public_reason(c, inflate_run(c->inf, ordered_stream(c), in, in_len, start_bit, end_bit, out, dict_len,
-                                        out_cap, out_len, consumed_bits, flags, deferred, &c->last_ms, partial));
+    Decode d{c->inf, ordered_stream(c)};
+    d.start_bit = start_bit; d.end_bit = end_bit; d.out = out; d.dict_len = dict_len; d.out_cap = out_cap;
+    d.flags = flags; d.deferred = deferred; d.partial = partial;
+    return run_decode(c, d, in, in_len, out_len, consumed_bits);
 }
 
 int ndfl_inflate_sync(ndfl_ctx* c, const uint8_t* in, uint64_t in_len, uint64_t from_bit, uint64_t window_bits,
                       uint64_t* sync_bit, uint32_t flags) {
     if (!c || !sync_bit || (!in && in_len) || from_bit > in_len * 8) return NDFL_E_ARG;
     HIPCHK(hipSetDevice(c->device));
-    return inflate_sync(c->inf, ordered_stream(c), in, in_len, from_bit, window_bits, flags, sync_bit, &c->last_ms);
+    Decode d{c->inf, ordered_stream(c)};                        // at or past from_bit, at most window_bits ahead
+    d.start_bit = from_bit; d.end_bit = std::min(in_len * 8, from_bit + window_bits); d.flags = flags;
+    return d.sync_probe(in, in_len, sync_bit);
 }
 
 int ndfl_inflate_headers(ndfl_ctx* c, const uint8_t* in, uint64_t in_len, uint32_t flags, uint64_t* headers,
                          uint64_t cap, uint64_t* n_headers, uint64_t* survivors, uint64_t surv_cap, uint64_t* stats) {
     if (!c || !n_headers || (!in && in_len) || (!headers && cap) || (!survivors && surv_cap)) return NDFL_E_ARG;
     HIPCHK(hipSetDevice(c->device));
-    const int r = inflate_headers(c->inf, ordered_stream(c), in, in_len, flags, headers, cap, n_headers, survivors,
-                                  surv_cap, stats);
-    return r == -4 ? NDFL_E_DEVICE : r < 0 ? NDFL_E_INTERNAL : r;
+    return batch_status(inflate_headers(c->inf, ordered_stream(c), in, in_len, flags, headers, cap, n_headers, survivors,
+                                        surv_cap, stats));
 }
 
 int ndfl_inflate_resolve(ndfl_ctx* c, uint64_t* n_reemitted) {
@@ -579,15 +578,13 @@ int ndfl_inflate_resolve(ndfl_ctx* c, uint64_t* n_reemitted) {
 int ndfl_inflate_tail(ndfl_ctx* c, uint64_t tail_len, uint8_t* dst) {
     if (!c || (!dst && tail_len)) return NDFL_E_ARG;
     HIPCHK(hipSetDevice(c->device));
-    const int r = inflate_tail(c->inf, ordered_stream(c), tail_len, dst);
-    return r == -5 ? NDFL_E_STATE : r == -6 ? NDFL_E_UNSUPPORTED : r == -1 ? NDFL_E_ARG : r;
+    return inflate_tail(c->inf, ordered_stream(c), tail_len, dst);
 }
 
 int ndfl_inflate_tail_map(ndfl_ctx* c, uint64_t tail_len, uint32_t* dst) {
     if (!c || (!dst && tail_len)) return NDFL_E_ARG;
     HIPCHK(hipSetDevice(c->device));
-    const int r = inflate_tail_map(c->inf, ordered_stream(c), tail_len, dst);
-    return r == -5 ? NDFL_E_STATE : r == -6 ? NDFL_E_UNSUPPORTED : r == -1 ? NDFL_E_ARG : r;
+    return inflate_tail_map(c->inf, ordered_stream(c), tail_len, dst);
 }
 
 int ndfl_bits_shift(ndfl_ctx* c, const uint8_t* in, uint64_t nbits, uint32_t shift, uint8_t* out, uint64_t out_cap,

@@ -82,8 +82,8 @@ static int deflate_bgzf_run(ndfl_ctx* c, const uint8_t* in, uint64_t in_len, uin
     uint8_t* d_out = out;
     if (!out_dev && out_cap) {          // (a file that fits out_cap fits the bound too)
         const uint64_t room = std::min<uint64_t>(out_cap, ndfl_bgzf_bound(in_len, block_len));
-        HIPCHK(inf_ensure(&c->batch.d_out, &c->batch.d_out_cap, room));
-        d_out = (uint8_t*)c->batch.d_out;
+        HIPCHK(c->batch.d_out.ensure(room));
+        d_out = c->batch.d_out.as<uint8_t>();
     }
 
     HIPCHK(hipEventRecord(c->ev0, s));

@@ -662,12 +662,12 @@ struct BatchRleLaunch {
     }
 };
 
-// Host input of a deflate batch: the span of `in` the items cover, staged in *d_in.  *d_src = the
+// Host input of a deflate batch: the span of `in` the items cover, staged in d_in.  *d_src = the
 // kernel's `in` (item offsets are relative to it).
-static int stage_span(void** d_in, size_t* d_in_cap, hipStream_t s, const uint8_t* in, const ndfl_member_item* items,
+static int stage_span(DevBuf& d_in, hipStream_t s, const uint8_t* in, const ndfl_member_item* items,
                       uint32_t n, uint32_t flags, const uint8_t** d_src) {
     *d_src = in;
-    if (flags & 1u) return 0;
+    if (flags & NDFL_IN_DEVICE) return 0;
     uint64_t lo = ~0ull, hi = 0;
     for (uint32_t i = 0; i < n; i++) {
         if (!items[i].in_len) continue;
@@ -675,20 +675,20 @@ static int stage_span(void** d_in, size_t* d_in_cap, hipStream_t s, const uint8_
         hi = std::max(hi, items[i].in_off + items[i].in_len);
     }
     if (hi > lo) {
-        INF_CHK(inf_ensure(d_in, d_in_cap, hi - lo));
-        INF_CHK(hipMemcpyAsync(*d_in, in + lo, hi - lo, hipMemcpyHostToDevice, s));
+        INF_CHK(d_in.ensure(hi - lo));
+        INF_CHK(hipMemcpyAsync(d_in.p, in + lo, hi - lo, hipMemcpyHostToDevice, s));
     }
-    *d_src = (const uint8_t*)*d_in - (hi > lo ? lo : 0);
+    *d_src = d_in.as<const uint8_t>() - (hi > lo ? lo : 0);
     return 0;
 }
 
 // ndfl_deflate_batch and ndfl_deflate_batch_lz77 on stream s (arguments already validated).  `launch`: a
 // BatchRleLaunch, or deflate_batch_lz.hip's BatchLzLaunch.
 template <class Launch>
-static int deflate_batch_run(BatchScratch& B, void** d_in, size_t* d_in_cap, hipStream_t s, hipEvent_t e0, hipEvent_t e1,
+static int deflate_batch_run(BatchScratch& B, DevBuf& d_in, hipStream_t s, hipEvent_t e0, hipEvent_t e1,
                              const uint8_t* in, uint8_t* out, const ndfl_member_item* items,
                              ndfl_deflate_result* results, uint32_t n, uint32_t flags, Launch launch, double* last_ms) {
-    INF_RC(stage_span(d_in, d_in_cap, s, in, items, n, flags, &launch.a.in));
+    INF_RC(stage_span(d_in, s, in, items, n, flags, &launch.a.in));
     INF_RC(launch.prepare());
     return batch_run(B, s, e0, e1, out, items, results, n, flags, last_ms, launch);
 }

@@ -484,12 +484,8 @@ ndfl_deflate_batch_lz_kernel(dblz::Args a) {
 // ---- host side ------------------------------------------------------------------------------------
 // The link rings and token lists of the grid's waves: grown on demand, kept by the context.
 struct BatchLzScratch {
-    void* d_mem = nullptr; size_t d_mem_cap = 0;
-    void release() {
-        if (d_mem) hipFree(d_mem);
-        d_mem = nullptr;
-        d_mem_cap = 0;
-    }
+    DevBuf d_mem;
+    void release() { d_mem.release(); }
 };
 
 // The most device memory the rings and token lists may take; the grid is lowered to fit.
@@ -545,10 +541,10 @@ struct BatchLzLaunchT {
         for (uint32_t i = 0; i < a.n; i++) longest = std::max(longest, items[i].in_len);
         const BatchLzSizes z = batch_lz_sizes(longest, a.chunk_len, a.hist_limit, LINKED_WHOLE, n_lists);
         grid = batch_grid<KERNEL>(a.n, knobs, LABEL, z.per_wave, BATCH_LZ_BUDGET);
-        if (z.per_wave) INF_CHK(inf_ensure(&Z.d_mem, &Z.d_mem_cap, (size_t)grid * z.per_wave));
+        if (z.per_wave) INF_CHK(Z.d_mem.ensure((size_t)grid * z.per_wave));
         a.tok_cap = z.tok_cap;
-        a.toks = (uint32_t*)Z.d_mem;
-        a.ring = (uint16_t*)((char*)Z.d_mem + (size_t)grid * z.tok_cap * 4 * n_lists); a.ring_mask = z.ring - 1;
+        a.toks = Z.d_mem.as<uint32_t>();
+        a.ring = (uint16_t*)(Z.d_mem.as<char>() + (size_t)grid * z.tok_cap * 4 * n_lists); a.ring_mask = z.ring - 1;
         return 0;
     }
     int operator()(hipStream_t s, uint8_t* d_out, const ndfl_member_item* d_items, ndfl_deflate_result* d_res,

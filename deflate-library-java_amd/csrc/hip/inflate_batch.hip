@@ -385,14 +385,9 @@ ndfl_inflate_members_kernel(const uint32_t* w, uint8_t* out, const ndfl_member_i
 
 // ---- host side ------------------------------------------------------------------------------------
 struct BatchScratch {
-    void* d_items = nullptr; size_t d_items_cap = 0;   // the items, then the results, then the ticket
-    void* d_out = nullptr; size_t d_out_cap = 0;       // host-output staging
-    void release() {
-        if (d_items) hipFree(d_items);
-        if (d_out) hipFree(d_out);
-        d_items = d_out = nullptr;
-        d_items_cap = d_out_cap = 0;
-    }
+    DevBuf d_items;                                    // the items, then the results, then the ticket
+    DevBuf d_out;                                      // host-output staging
+    void release() { d_items.release(); d_out.release(); }
 };
 
 // The grid of a batch kernel (one-wave workgroups that claim streams from a ticket): what fits on the
@@ -401,7 +396,7 @@ struct BatchScratch {
 // the call in the NDFL_STATS line.
 template <auto Kernel>
 static uint32_t batch_grid(uint32_t n, const Knobs& knobs, const char* label, size_t per_wave = 0, size_t budget = 0) {
-    static const uint32_t auto_grid = wave_grid(Kernel, 256 * 16);
+    static const uint32_t auto_grid = occupancy_grid(Kernel, 64, 256 * 16);
     uint32_t grid = std::min(n, auto_grid);
     if (knobs.batch_waves) grid = std::min(grid, knobs.batch_waves);
     if (per_wave) grid = (uint32_t)std::max<size_t>(1, std::min<size_t>(grid, budget / per_wave));
@@ -424,10 +419,10 @@ template <class Item, class Result, class Launch>
 static int batch_run(BatchScratch& B, hipStream_t s, hipEvent_t e0, hipEvent_t e1, uint8_t* out, const Item* items,
                      Result* results, uint32_t n, uint32_t flags, double* last_ms, Launch&& launch) {
     const size_t items_b = (size_t)n * sizeof(Item), res_b = (size_t)n * sizeof(Result);
-    INF_CHK(inf_ensure(&B.d_items, &B.d_items_cap, items_b + res_b + 16));
-    Result* d_res = (Result*)((char*)B.d_items + items_b);
+    INF_CHK(B.d_items.ensure(items_b + res_b + 16));
+    Result* d_res = (Result*)(B.d_items.as<char>() + items_b);
     uint32_t* d_ticket = (uint32_t*)((char*)d_res + res_b);
-    INF_CHK(hipMemcpyAsync(B.d_items, items, items_b, hipMemcpyHostToDevice, s));
+    INF_CHK(hipMemcpyAsync(B.d_items.p, items, items_b, hipMemcpyHostToDevice, s));
     INF_CHK(hipMemsetAsync(d_ticket, 0, 16, s));
     uint64_t lo = ~0ull, hi = 0;                 // the span of `out` the regions cover
     for (uint32_t i = 0; i < n; i++) {
@@ -435,21 +430,21 @@ static int batch_run(BatchScratch& B, hipStream_t s, hipEvent_t e0, hipEvent_t e
         lo = std::min(lo, items[i].out_off);
         hi = std::max(hi, items[i].out_off + items[i].out_cap);
     }
-    const bool out_dev = (flags & 2u) != 0;
+    const bool out_dev = (flags & NDFL_OUT_DEVICE) != 0;
     uint8_t* d_out = out;
     std::vector<uint8_t> h_span;
     if (!out_dev) {
-        if (hi > lo) INF_CHK(inf_ensure(&B.d_out, &B.d_out_cap, hi - lo));
-        d_out = (uint8_t*)B.d_out - (hi > lo ? lo : 0);
+        if (hi > lo) INF_CHK(B.d_out.ensure(hi - lo));
+        d_out = B.d_out.as<uint8_t>() - (hi > lo ? lo : 0);
     }
     INF_CHK(hipEventRecord(e0, s));
-    INF_RC(launch(s, d_out, (const Item*)B.d_items, d_res, d_ticket));
+    INF_RC(launch(s, d_out, B.d_items.as<const Item>(), d_res, d_ticket));
     INF_CHK(hipGetLastError());
     INF_CHK(hipEventRecord(e1, s));
     INF_CHK(hipMemcpyAsync(results, d_res, res_b, hipMemcpyDeviceToHost, s));
     if (!out_dev && hi > lo) {
         h_span.resize(hi - lo);
-        INF_CHK(hipMemcpyAsync(h_span.data(), B.d_out, hi - lo, hipMemcpyDeviceToHost, s));
+        INF_CHK(hipMemcpyAsync(h_span.data(), B.d_out.p, hi - lo, hipMemcpyDeviceToHost, s));
     }
     INF_CHK(hipStreamSynchronize(s));
     float ms = 0;

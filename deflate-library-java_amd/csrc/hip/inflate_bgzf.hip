@@ -313,12 +313,12 @@ ndfl_bgzf_reduce_kernel(const ndfl_member_item* items, const ndfl_member_result*
 
 // ---- host side ------------------------------------------------------------------------------------
 struct BgzfScratch {
-    void* d = nullptr; size_t d_cap = 0;      // the head, the tile counts, the candidate list, the table
+    DevBuf d;                                 // the head, the tile counts, the candidate list, the table
     hipEvent_t ev_mid = nullptr;              // between the layout and the decode
     void release() {
-        if (d) hipFree(d);
+        d.release();
         if (ev_mid) hipEventDestroy(ev_mid);
-        d = nullptr; d_cap = 0; ev_mid = nullptr;
+        ev_mid = nullptr;
     }
 };
 
@@ -367,10 +367,10 @@ static int inflate_bgzf_run(InflateScratch& S, BatchScratch& B, BgzfScratch& Z, 
                      o_clen = o_cpos + up(cap * 8), o_ja = o_clen + up(cap * 4), o_jb = o_ja + up(cap * 4),
                      o_mark = o_jb + up(cap * 4), o_lcnt = o_mark + up(cap * 4), o_lsum = o_lcnt + up((size_t)ltiles * 4),
                      o_table = o_lsum + up((size_t)ltiles * 8), o_end = o_table + up((cap + 1) * sizeof(ndfl_bgzf_member));
-        INF_CHK(inf_ensure(&Z.d, &Z.d_cap, o_end));
+        INF_CHK(Z.d.ensure(o_end));
         const size_t items_b = cap * sizeof(ndfl_member_item), res_b = cap * sizeof(ndfl_member_result);
-        INF_CHK(inf_ensure(&B.d_items, &B.d_items_cap, items_b + res_b + 16));
-        char* z = (char*)Z.d;
+        INF_CHK(B.d_items.ensure(items_b + res_b + 16));
+        char* z = Z.d.as<char>();
         d_head = (Head*)(z + o_head);
         uint32_t* d_tcnt = (uint32_t*)(z + o_tcnt);
         uint64_t* d_cpos = (uint64_t*)(z + o_cpos);
@@ -381,8 +381,8 @@ static int inflate_bgzf_run(InflateScratch& S, BatchScratch& B, BgzfScratch& Z, 
         uint32_t* d_lcnt = (uint32_t*)(z + o_lcnt);
         uint64_t* d_lsum = (uint64_t*)(z + o_lsum);
         d_table = (ndfl_bgzf_member*)(z + o_table);
-        d_items = (ndfl_member_item*)B.d_items;
-        d_res = (ndfl_member_result*)((char*)B.d_items + items_b);
+        d_items = B.d_items.as<ndfl_member_item>();
+        d_res = (ndfl_member_result*)(B.d_items.as<char>() + items_b);
         d_ticket = (uint32_t*)((char*)d_res + res_b);
         INF_CHK(hipMemsetAsync(d_head, 0, up(sizeof(Head)), s));
         INF_CHK(hipMemsetAsync(d_ticket, 0, 16, s));
@@ -420,7 +420,7 @@ static int inflate_bgzf_run(InflateScratch& S, BatchScratch& B, BgzfScratch& Z, 
             INF_CHK(hipMemcpyAsync(h_table.data(), d_table, h_table.size() * sizeof(ndfl_bgzf_member), hipMemcpyDeviceToHost, s));
         INF_CHK(hipStreamSynchronize(s));
         if (h.n_cand <= cap) break;
-        if (pass) return -6;                              // (the second list has room for every candidate)
+        if (pass) return NDFL_E_INTERNAL;                             // (the second list has room for every candidate)
         cap = h.n_cand;
         if (S.knobs.stats) fprintf(stderr, "[ndfl] inflate bgzf: %u candidates, scanning again\n", h.n_cand);
     }
@@ -440,12 +440,12 @@ static int inflate_bgzf_run(InflateScratch& S, BatchScratch& B, BgzfScratch& Z, 
         if (hipEventElapsedTime(&ms, e0, Z.ev_mid) == hipSuccess) { *last_ms = ms; S.last_ms_find = ms; S.last_ms_emit = 0; }
         return 0;
     }
-    const bool out_dev = (flags & 2u) != 0;
+    const bool out_dev = (flags & NDFL_OUT_DEVICE) != 0;
     const uint64_t total = h.total;
     uint8_t* d_out = out;
     if (!out_dev && total) {
-        INF_CHK(inf_ensure(&B.d_out, &B.d_out_cap, total));
-        d_out = (uint8_t*)B.d_out;
+        INF_CHK(B.d_out.ensure(total));
+        d_out = B.d_out.as<uint8_t>();
     }
     const uint32_t grid = batch_grid<ndfl_inflate_members_kernel>(n, S.knobs, "inflate bgzf");
     hipLaunchKernelGGL(ndfl_inflate_members_kernel, dim3(grid), dim3(64), 0, s, d_w, d_out, d_items, d_res, n, d_ticket,

@@ -22,15 +22,13 @@
 // conflict-free for any per-lane index), and the dynamic header is parsed in two passes over the
 // stream bits so that no per-lane array (private scratch memory) is ever needed.
 // Errors are the reference's DataFormatException Reasons, checked in the reference's order; the
-// first error in stream order wins.
+// first error in stream order wins.  The host side of a decode: csrc/capi/ndfl_inflate.cpp.
 // D/ = /root/reference/src/io/nayuki/deflate/
 #pragma once
 #include "ndfl_common.hpp"
 #include "../../../include/ndfl.h"
 #include <vector>
 #include <algorithm>
-#include <unordered_map>
-#include <chrono>
 #include <string.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -88,7 +86,7 @@ constexpr uint32_t STRICT_SLICE = NDFL_STRICT_SLICE;  // strict stage: survivors
 #define NDFL_COUNT_W_DEFAULT 1
 #endif
 constexpr uint32_t COUNT_WAVES = 256 * 16;       // count / emit passes: persistent waves at most (the
-constexpr uint32_t EMIT_WAVES = 256 * 16;        // grids are sized by occupancy, wave_grid below)
+constexpr uint32_t EMIT_WAVES = 256 * 16;        // grids are sized by occupancy, ndfl_inflate.cpp)
 
 struct In {
     const uint32_t* w;
@@ -1119,1107 +1117,6 @@ ndfl_inflate_alias_copy_kernel(const uint32_t* rep, uint32_t n, ChainRes* res, S
     }
 }
 
-// ---- host orchestration ---------------------------------------------------------------------
-
-struct InflateScratch {
-    void* d_in = nullptr; size_t d_in_cap = 0;
-    void* d_cand = nullptr; size_t d_cand_cap = 0;
-    void* d_starts = nullptr; size_t d_starts_cap = 0;
-    void* d_stops = nullptr; size_t d_stops_cap = 0;
-    void* d_res = nullptr; size_t d_res_cap = 0;
-    void* d_cands = nullptr; size_t d_cands_cap = 0;
-    void* d_stats = nullptr;
-    void* d_q = nullptr; size_t d_q_cap = 0;           // finder survivors (stage 1 -> stage 2)
-    void* d_seg = nullptr; size_t d_seg_cap = 0;      // segment record pool (SegPool)
-    SegPool pool{};
-    void* d_chains = nullptr; size_t d_chains_cap = 0;
-    void* d_off = nullptr; size_t d_off_cap = 0;
-    void* d_ref = nullptr; size_t d_ref_cap = 0;      // emit: back-reference per output byte (deferred copies)
-    void* d_pend = nullptr; size_t d_pend_cap = 0;    // emit: pending bit per output byte
-    void* d_rl = nullptr; size_t d_rl_cap = 0;        // resolve: two group lists + round bits
-    void* d_ticket = nullptr;
-    void* d_slow = nullptr; size_t d_slow_cap = 0;    // emit: chains the fast emit pass leaves to the full one
-    void* d_rep = nullptr; size_t d_rep_cap = 0;      // count: the candidate counted for each (stored-header aliases)
-    void* d_ph = nullptr;                             // count pass: phase-fallback slot per wave
-    void* d_hrec = nullptr;                           // count pass: header records, one per candidate
-    size_t d_hrec_cap = 0;
-    void* d_cticket = nullptr;                        // count pass: chain tickets (one per launch)
-    void* d_out = nullptr; size_t d_out_cap = 0;
-    Knobs knobs;                                       // the context's switches (ndfl_common.hpp)
-    uint32_t q_cap = 0, q_min = 0;                    // finder survivor list: capacity of the last scan / asked minimum
-    bool q_full = false;                              //   the last scan's list could not grow (budget, allocation)
-    double last_ms_find = 0, last_ms_count = 0, last_ms_emit = 0, last_ms_wall = 0;
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    uint64_t repairs = 0, chains = 0, candidates = 0, resolved_groups = 0, flat_chains = 0;
-    uint64_t pending_after_dev = 0;                   // 32-byte groups still pending after the device-queued resolve rounds
-    void* h_cnt = nullptr;                            // pinned: resolve list size
-    void* d_info = nullptr;                           // device-side linking: summary (LI_*)
-    void* h_info = nullptr;                           //   and its pinned host copy
-    void* d_link = nullptr; size_t d_link_cap = 0;    //   pointer-jumping levels and sums
-    bool count_first = false;
-    // state kept for ndfl_inflate_resolve after a deferred-window range decode
-    bool pending = false;
-    uint8_t* p_out = nullptr;
-    uint64_t p_nbytes = 0, p_dict_len = 0;
-    void release() {
-        void** ps[] = {&d_in, &d_cand, &d_starts, &d_stops, &d_res, &d_cands, &d_stats, &d_q, &d_seg, &d_chains, &d_off,
-                       &d_ref, &d_pend, &d_rl, &d_ticket, &d_ph, &d_cticket, &d_out, &d_hrec, &d_slow, &d_rep};
-        for (void** p : ps) { if (*p) hipFree(*p); *p = nullptr; }
-        for (auto& e : ev) { if (e) hipEventDestroy(e); e = nullptr; }
-        if (h_cnt) hipHostFree(h_cnt);
-        h_cnt = nullptr;
-        if (h_info) hipHostFree(h_info);
-        h_info = nullptr;
-        if (d_info) hipFree(d_info);
-        d_info = nullptr;
-        if (d_link) hipFree(d_link);
-        d_link = nullptr; d_link_cap = 0;
-        d_in_cap = d_cand_cap = d_starts_cap = d_stops_cap = d_res_cap = d_cands_cap = d_seg_cap = d_q_cap = d_chains_cap = 0;
-        d_off_cap = d_ref_cap = d_pend_cap = d_rl_cap = d_out_cap = d_hrec_cap = 0;
-        pending = false;
-    }
-};
-
-// Persistent-wave grid of a one-wave-workgroup kernel: what fits on the chip at once (occupancy),
-// at most `cap` waves.
-template <typename K>
-static uint32_t wave_grid(K kernel, uint32_t cap, const char* env = nullptr) {
-    int dev = 0, ncu = 0, per = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kernel, 64, 0) != hipSuccess || ncu <= 0 || per <= 0)
-        return cap;
-    if (env && getenv(env)) per = std::max(1, atoi(getenv(env)));     // waves per CU override (tuning)
-    return std::min<uint32_t>(cap, (uint32_t)(ncu * per));
-}
-
-// The count pass: one wave per chain (W = 1) or W waves per chain (workgroup rounds,
-// inflate_wg.hpp); NDFL_COUNT_W selects W (1, 2, 4, 8).  Persistent grid sized by occupancy; the
-// phase-fallback slots (d_ph) cover COUNT_WAVES waves.
-static uint32_t count_w(const Knobs& k) {
-    const uint32_t v = k.count_w ? k.count_w : (uint32_t)NDFL_COUNT_W_DEFAULT;
-    return (v == 2 || v == 4 || v == 8) ? v : 1u;
-}
-template <typename K>
-static uint32_t wg_grid(K kernel, uint32_t threads, uint32_t cap) {
-    int dev = 0, ncu = 0, per = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kernel, (int)threads, 0) != hipSuccess || ncu <= 0 || per <= 0)
-        return cap;
-    return std::min<uint32_t>(cap, (uint32_t)(ncu * per));
-}
-template <typename... A>
-static void launch_count(hipStream_t s, uint32_t W, uint32_t nchains, A... args) {
-    if (W == 1) {
-        static const uint32_t g1 = wave_grid(ndfl_inflate_count_wave_kernel, inf::COUNT_WAVES, "NDFL_COUNT_WPC");
-        hipLaunchKernelGGL(ndfl_inflate_count_wave_kernel, dim3(std::min(nchains, g1)), dim3(64), 0, s, args...);
-    } else if (W == 2) {
-        static const uint32_t g = wg_grid(ndfl_inflate_count_wg_kernel<2>, 128, inf::COUNT_WAVES / 2);
-        hipLaunchKernelGGL(ndfl_inflate_count_wg_kernel<2>, dim3(std::min(nchains, g)), dim3(128), 0, s, args...);
-    } else if (W == 4) {
-        static const uint32_t g = wg_grid(ndfl_inflate_count_wg_kernel<4>, 256, inf::COUNT_WAVES / 4);
-        hipLaunchKernelGGL(ndfl_inflate_count_wg_kernel<4>, dim3(std::min(nchains, g)), dim3(256), 0, s, args...);
-    } else {
-        static const uint32_t g = wg_grid(ndfl_inflate_count_wg_kernel<8>, 512, inf::COUNT_WAVES / 8);
-        hipLaunchKernelGGL(ndfl_inflate_count_wg_kernel<8>, dim3(std::min(nchains, g)), dim3(512), 0, s, args...);
-    }
-}
-
-static hipError_t inf_ensure(void** p, size_t* cap, size_t n) {
-    if (n <= *cap && *p) return hipSuccess;
-    if (*p) { hipFree(*p); *p = nullptr; *cap = 0; }
-    size_t want = n < 4096 ? 4096 : n;
-    hipError_t e = hipMalloc(p, want);
-    if (e == hipSuccess) *cap = want;
-    return e;
-}
-
-
-static bool inf_debug() { static const bool d = getenv("NDFL_DEBUG") != nullptr; return d; }
-#define INF_CHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) {                                             \
-        if (inf_debug()) fprintf(stderr, "[ndfl] HIP error %d (%s) at inflate_kernels.hip:%d\n", (int)_e,     \
-                                 hipGetErrorString(_e), __LINE__);                                              \
-        return -4; } } while (0)
-#define INF_RC(x) do { const int _r = (x); if (_r) return _r; } while (0)
-
-// Resolve the deferred copies of an emit pass: pointer-jumping rounds over the pending 32-byte
-// groups of out[0, nbytes) until none is left.  *groups = pending groups at the start.
-static int resolve_rounds(InflateScratch& S, hipStream_t s, uint8_t* d_out, uint64_t nbytes, uint64_t* groups) {
-    using namespace inf;
-    *groups = 0;
-    const uint64_t npw = (nbytes + 31) / 32;
-    if (npw == 0) return 0;
-    if (npw > 0xFFFFFFFFull) return -2;
-    INF_CHK(inf_ensure(&S.d_rl, &S.d_rl_cap, npw * 12 + 64));
-    uint32_t* cnt = (uint32_t*)S.d_rl;                       // [0], [1]: list sizes
-    uint32_t* lst[2] = {(uint32_t*)((char*)S.d_rl + 64), (uint32_t*)((char*)S.d_rl + 64) + npw};
-    uint32_t* nb = lst[1] + npw;
-    uint32_t* pend = (uint32_t*)S.d_pend;
-    uint32_t* ref = (uint32_t*)S.d_ref;
-    INF_CHK(hipMemsetAsync(cnt, 0, 8, s));
-    hipLaunchKernelGGL(ndfl_inflate_pending_list_kernel, dim3((uint32_t)((npw + 4095) / 4096)), dim3(256), 0, s,
-                       (const uint32_t*)pend, (uint64_t)0, npw, lst[0], cnt);
-    INF_CHK(hipGetLastError());
-    if (!S.h_cnt) INF_CHK(hipHostMalloc(&S.h_cnt, 64, 0));
-    uint32_t* h = (uint32_t*)S.h_cnt;
-    // rounds are queued four at a time on grid-stride kernels; the host reads the list size between
-    // batches only (pointer jumping needs ~log2(reference depth) rounds)
-    int cur = 0;
-    uint32_t n = 0;
-    for (int round = 0;; round++) {
-        const bool rstats = S.knobs.stats;
-        if ((round & 3) == 0 || rstats) {
-            INF_CHK(hipMemcpyAsync(h, cnt + cur, 4, hipMemcpyDeviceToHost, s));
-            if (rstats) INF_CHK(hipMemcpyAsync(h + 1, cnt + 2 + cur, 4, hipMemcpyDeviceToHost, s));
-            INF_CHK(hipStreamSynchronize(s));
-            n = *h;
-            if (rstats) fprintf(stderr, "[ndfl] resolve round %d: %u pending groups, %u bytes\n", round, n, h[1]);
-            if (round == 0) *groups = n;
-            if (n == 0) return 0;
-            if (round >= 96) return R_INTERNAL;              // distances double each round: unreachable
-        }
-        INF_CHK(hipMemsetAsync(cnt + (cur ^ 1), 0, 4, s));
-        if (rstats) INF_CHK(hipMemsetAsync(cnt + 2 + (cur ^ 1), 0, 4, s));
-        const uint32_t gb = (uint32_t)std::min<uint64_t>(4096, ((uint64_t)n * 32 + 255) / 256);
-        hipLaunchKernelGGL(ndfl_inflate_resolve_kernel, dim3(gb), dim3(256), 0, s,
-                           (const uint32_t*)lst[cur], (const uint32_t*)(cnt + cur), (const uint32_t*)pend, ref, d_out, nb);
-        INF_CHK(hipGetLastError());
-        hipLaunchKernelGGL(ndfl_inflate_resolve_apply_kernel, dim3((uint32_t)std::min<uint64_t>(1024, (n + 255) / 256)),
-                           dim3(256), 0, s, (const uint32_t*)lst[cur], (const uint32_t*)(cnt + cur), pend,
-                           (const uint32_t*)nb, lst[cur ^ 1], cnt + (cur ^ 1), rstats ? cnt + 2 + (cur ^ 1) : (uint32_t*)nullptr);
-        INF_CHK(hipGetLastError());
-        cur ^= 1;
-    }
-}
-
-// NDFL_STATS: the strict stage's counters and the count pass's wave clocks, from d_stats (both decode
-// paths print them)
-static int print_count_stats(InflateScratch& S, bool phase_clock_note) {
-    uint32_t st[64] = {0};
-    INF_CHK(hipMemcpy(st, S.d_stats, 256, hipMemcpyDeviceToHost));
-    const unsigned long long* ss = (const unsigned long long*)(st + SW_STRICT64);
-    fprintf(stderr, "[ndfl] strict stage: %llu waves, %llu loop trips (%llu refills), %llu lane-symbol steps\n",
-            ss[3], ss[0], ss[1], ss[2]);
-    const uint64_t* t64 = (const uint64_t*)(st + SW_CLOCK64);
-    fprintf(stderr, "[ndfl] count wave-time (ms x waves, 100 MHz clock%s): header %.1f spec %.1f "
-            "verify %.1f phases %.1f serial %.1f record %.1f build %.1f phase-mapped %.1f\n",
-            phase_clock_note ? "; -DNDFL_PHASE_CLOCK builds" : "", t64[0] * 1e-5,
-            t64[1] * 1e-5, t64[2] * 1e-5, t64[3] * 1e-5, t64[4] * 1e-5, t64[5] * 1e-5, t64[6] * 1e-5, t64[7] * 1e-5);
-    const double span = (double)(t64[9] - ~t64[10]);
-    fprintf(stderr, "[ndfl] count waves %llu: busy %.1f ms x waves, span %.3f ms, occupancy %.3f, longest chain %.3f ms\n",
-            (unsigned long long)t64[11], t64[8] * 1e-5, span * 1e-5, t64[11] ? t64[8] / (span * t64[11]) : 0.0,
-            t64[12] * 1e-5);
-    return 0;
-}
-
-// Segment-record pool for `nstarts` chain starts (SegPool): the rounds of all chains, one head per
-// counted chain start, with room for repairs, and the per-block table records.
-static int setup_pool(InflateScratch& S, hipStream_t s, uint64_t nstarts, uint64_t nbits) {
-    using namespace inf;
-    const uint64_t nslot = nstarts + std::max<uint64_t>(4096, nstarts / 2);
-    const uint64_t nrec = std::min<uint64_t>(0xFFFFFFF0ull, 2 * nstarts + nbits / (wv::MAX_SPAN / 2) + 65536);
-    // table records: at most one per block; bounded (a stream of tiny blocks parses the rest again)
-    const uint64_t nbt = std::min<uint64_t>(nrec, S.knobs.no_bt ? 0 : (1u << 18));
-    const uint64_t seg_bytes = nrec * (64 * 8 + 64 * 4 + sizeof(SegMeta)) + nslot * 4 + 64 + nbt * BT_BYTES;
-    INF_CHK(inf_ensure(&S.d_seg, &S.d_seg_cap, seg_bytes));
-    SegPool pool;
-    pool.start = (uint64_t*)S.d_seg;
-    pool.cnt = (uint32_t*)(pool.start + nrec * 64);
-    pool.meta = (SegMeta*)(pool.cnt + nrec * 64);
-    pool.head = (uint32_t*)(pool.meta + nrec);
-    pool.ctr = (uint32_t*)S.d_stats + SW_REC_CTR;
-    pool.bctr = (uint32_t*)S.d_stats + SW_TREC_CTR;
-    pool.nbt = (uint32_t)nbt;
-    pool.bt = (TabRec*)(((uintptr_t)(pool.head + nslot) + 63) & ~(uintptr_t)63);
-    pool.nrec = (uint32_t)nrec;
-    pool.nslot = nslot;
-    S.pool = pool;
-    INF_CHK(hipMemsetAsync(pool.head, 0xFF, nslot * 4, s));
-    return 0;
-}
-
-// Queue `rounds` resolve rounds without reading anything back (the kernels read the list sizes on
-// the device; a round with nothing pending costs two empty launches).  *cnt_slot = where the size of
-// the list left after them is (cnt + cur).
-static int resolve_rounds_dev(InflateScratch& S, hipStream_t s, uint8_t* d_out, uint64_t nbytes, int rounds,
-                              uint32_t** left, uint64_t* first_count_dst) {
-    using namespace inf;
-    const uint64_t npw = (nbytes + 31) / 32;
-    *left = nullptr;
-    if (npw == 0) return 0;
-    if (npw > 0xFFFFFFFFull) return -2;
-    INF_CHK(inf_ensure(&S.d_rl, &S.d_rl_cap, npw * 12 + 64));
-    uint32_t* cnt = (uint32_t*)S.d_rl;
-    uint32_t* lst[2] = {(uint32_t*)((char*)S.d_rl + 64), (uint32_t*)((char*)S.d_rl + 64) + npw};
-    uint32_t* nb = lst[1] + npw;
-    uint32_t* pend = (uint32_t*)S.d_pend;
-    uint32_t* ref = (uint32_t*)S.d_ref;
-    INF_CHK(hipMemsetAsync(cnt, 0, 8, s));
-    hipLaunchKernelGGL(ndfl_inflate_pending_list_kernel, dim3((uint32_t)((npw + 4095) / 4096)), dim3(256), 0, s,
-                       (const uint32_t*)pend, (uint64_t)0, npw, lst[0], cnt);
-    INF_CHK(hipGetLastError());
-    if (first_count_dst) INF_CHK(hipMemcpyAsync(first_count_dst, cnt, 4, hipMemcpyDeviceToDevice, s));
-    int cur = 0;
-    for (int round = 0; round < rounds; round++) {
-        INF_CHK(hipMemsetAsync(cnt + (cur ^ 1), 0, 4, s));
-        hipLaunchKernelGGL(ndfl_inflate_resolve_kernel, dim3(4096), dim3(256), 0, s, (const uint32_t*)lst[cur],
-                           (const uint32_t*)(cnt + cur), (const uint32_t*)pend, ref, d_out, nb);
-        INF_CHK(hipGetLastError());
-        hipLaunchKernelGGL(ndfl_inflate_resolve_apply_kernel, dim3(1024), dim3(256), 0, s, (const uint32_t*)lst[cur],
-                           (const uint32_t*)(cnt + cur), pend, (const uint32_t*)nb, lst[cur ^ 1], cnt + (cur ^ 1),
-                           (uint32_t*)nullptr);
-        INF_CHK(hipGetLastError());
-        cur ^= 1;
-    }
-    *left = cnt + cur;
-    return 0;
-}
-
-constexpr int LINK_FALLBACK = 1000;      // the device-side path hands over to the host path
-constexpr int FIND_OVERFLOW = 1001;      // more finder survivors than the list held: scan again
-constexpr uint32_t LI_QCOUNT = 14;       // (host copy only: the finder's survivor count)
-
-// The decode after the header finder with everything on the device and ONE host synchronization
-// in the middle (the number of chain starts, which sizes the record pool and the grids) and one at
-// the end (the summary): candidate list (segment scan, compaction, the range's slice), the count
-// pass in longest-first order, chain linking by pointer jumping, the emit pass, the first error,
-// the resolve rounds.  Returns LINK_FALLBACK when the host's linking has to step in (a chain that
-// stopped at a boundary that is no candidate) -- the host path then starts over from the finder's
-// candidates -- or when the list of chain starts is too long for the jump tables.
-static int inflate_devlink(InflateScratch& S, hipStream_t s, const uint32_t* d_w, uint64_t nwords, uint64_t nbits,
-                           uint32_t nseg, const uint32_t* d_cnt, const uint64_t* d_list, uint64_t start_bit,
-                           uint64_t end_bit, uint8_t* out, uint64_t dict_len, uint64_t out_cap, uint64_t* out_len,
-                           uint64_t* consumed_bits, uint32_t flags, bool deferred, bool partial, double* last_ms) {
-    using namespace inf;
-    if (!S.d_info) INF_CHK(hipMalloc(&S.d_info, LI_WORDS * 8));
-    if (!S.h_info) INF_CHK(hipHostMalloc(&S.h_info, LI_WORDS * 8, 0));
-    uint64_t* info = (uint64_t*)S.d_info;
-    volatile uint64_t* hinfo = (volatile uint64_t*)S.h_info;
-    INF_CHK(hipMemsetAsync(info, 0, LI_WORDS * 8, s));
-    const uint64_t cap_all = (uint64_t)nseg * SEG_CAP + 1;      // the sorted list's length at most
-    const uint32_t ntile = (nseg + SCAN_TILE - 1) / SCAN_TILE;
-    INF_CHK(inf_ensure(&S.d_starts, &S.d_starts_cap, (cap_all + nseg + 2 + ntile) * 8));
-    uint64_t* d_sorted = (uint64_t*)S.d_starts;
-    uint64_t* d_segoff = d_sorted + cap_all;
-    uint64_t* d_part = d_segoff + nseg + 2;
-    hipLaunchKernelGGL(ndfl_inflate_segsum_kernel, dim3(ntile), dim3(SCAN_T), 0, s, d_cnt, nseg, d_part);
-    INF_CHK(hipGetLastError());
-    hipLaunchKernelGGL(ndfl_inflate_segscan_kernel, dim3(ntile), dim3(SCAN_T), 0, s, d_cnt, nseg, d_segoff, info,
-                       (const uint64_t*)d_part);
-    INF_CHK(hipGetLastError());
-    hipLaunchKernelGGL(ndfl_inflate_compact_kernel, dim3((nseg + 3) / 4), dim3(256), 0, s, d_cnt, d_list,
-                       (const uint64_t*)d_segoff, nseg, d_sorted);
-    INF_CHK(hipGetLastError());
-    INF_CHK(inf_ensure(&S.d_cands, &S.d_cands_cap, (cap_all + 1) * 8ull));
-    hipLaunchKernelGGL(ndfl_inflate_cand_slice_kernel, dim3((uint32_t)std::min<uint64_t>(4096, (cap_all + 255) / 256)),
-                       dim3(256), 0, s, (const uint64_t*)d_sorted, info, start_bit, end_bit, (uint64_t*)S.d_cands);
-    INF_CHK(hipGetLastError());
-    // stored-header aliases counted once (NDFL_NO_ALIAS: every candidate counted)
-    const bool alias_on = !S.knobs.no_alias;
-    uint32_t* d_rep = nullptr;
-    if (alias_on) {
-        INF_CHK(inf_ensure(&S.d_rep, &S.d_rep_cap, (size_t)cap_all * 4 + 64));
-        d_rep = (uint32_t*)S.d_rep;
-        hipLaunchKernelGGL(ndfl_inflate_alias_mark_kernel, dim3((uint32_t)std::min<uint64_t>(1024, (cap_all + 255) / 256)),
-                           dim3(256), 0, s, (const uint64_t*)S.d_cands, info, d_w, nwords, nbits, d_rep);
-        INF_CHK(hipGetLastError());
-    }
-    INF_CHK(hipMemcpyAsync((void*)hinfo, info, (LI_NREP + 1) * 8, hipMemcpyDeviceToHost, s));
-    hinfo[LI_QCOUNT] = 0;
-    INF_CHK(hipMemcpyAsync((void*)(hinfo + LI_QCOUNT), (const uint32_t*)S.d_stats + SW_QCOUNT, 4, hipMemcpyDeviceToHost, s));
-    INF_CHK(hipStreamSynchronize(s));                          // (1) the number of chain starts
-    if ((uint32_t)hinfo[LI_QCOUNT] > S.q_cap && !S.q_full) { S.q_min = (uint32_t)hinfo[LI_QCOUNT] + 65536; return FIND_OVERFLOW; }
-    const uint64_t n = hinfo[LI_NCAND];
-    // the count pass's width: one wave per chain, unless the chains to count are few against the
-    // count waves (fewer than 2 per wave), where a chain's rounds in sequence bound the pass (config
-    // 2: 3,286 chains, ~1.1 per wave: 4 waves per chain count it in 2.0 ms instead of 4.0; one rank's
-    // 512 MiB share of the bench at 8 GPUs: 8,191 chains, ~2.7 per wave: one wave each, 2.1 ms
-    // instead of 3.1 -- profiles/r05_shard_count_width.txt; the bench's 66,770 chains: one wave
-    // each) -- NDFL_COUNT_W overrides
-    const uint64_t nrep = alias_on ? hinfo[LI_NREP] : n;
-    static const uint32_t count_waves = wave_grid(ndfl_inflate_count_wave_kernel, COUNT_WAVES, "NDFL_COUNT_WPC");
-    const uint32_t W = S.knobs.count_w ? count_w(S.knobs) : (nrep < 2ull * count_waves && nbits >= (1ull << 24)) ? 4u : 1u;
-    if (S.knobs.stats) fprintf(stderr, "[ndfl] count pass: %llu candidates, %llu counted, width %u\n",
-                                      (unsigned long long)n, (unsigned long long)nrep, W);
-    if (n == 0 || n > (1ull << 24)) return LINK_FALLBACK;
-    const uint32_t ncand = (uint32_t)n;
-    int rc = setup_pool(S, s, n, nbits);
-    if (rc) return rc;
-    // count pass, longest chains first
-    INF_CHK(inf_ensure(&S.d_stops, &S.d_stops_cap, n * 12));
-    INF_CHK(inf_ensure(&S.d_res, &S.d_res_cap, n * sizeof(ChainRes)));
-    uint32_t* d_order = (uint32_t*)((char*)S.d_stops + n * 8);
-    if (!S.d_cticket) INF_CHK(hipMalloc(&S.d_cticket, CTK_BYTES));
-    INF_CHK(hipMemsetAsync(S.d_cticket, 0, CTK_BYTES, s));
-    uint32_t* d_nord = (uint32_t*)S.d_cticket + CT_NORD;
-    uint32_t* d_nflat = (uint32_t*)S.d_cticket + CT_NFLAT;
-    uint32_t* d_ob = (uint32_t*)S.d_cticket + CT_ORDER;                    // count order: tot, cursor
-    const uint32_t otiles = (ncand + SCAN_TILE - 1) / SCAN_TILE;
-    if (!S.d_ph) INF_CHK(hipMalloc(&S.d_ph, (size_t)std::max(COUNT_WAVES, EMIT_WAVES) * sizeof(wv::PhArr)));
-    const bool stats_on = S.knobs.stats;
-    const uint64_t limit = std::min(end_bit, nbits);
-    INF_CHK(hipEventRecord(S.ev[2], s));
-    // header records, and the chains whose first block is counted by one lane (flat groups: the
-    // one-wave count kernel only); those leave the count order
-    const bool hrec_on = !S.knobs.no_hdrrec;
-    // (a flat group decodes its 64 blocks one lane each: ~7 ms of latency however few the chains, so
-    // only a pass long enough to hide it takes them -- the bench's 66,770 chains; one rank's 8,191 at
-    // 8 GPUs counts its incompressible blocks in wave form, by escape scans)
-    const bool flat_on = hrec_on && W == 1 && S.knobs.flat && nrep >= S.knobs.flat_min;
-    uint32_t* d_flist = nullptr;
-    uint32_t* d_fflag = nullptr;
-    if (hrec_on) {
-        INF_CHK(inf_ensure(&S.d_hrec, &S.d_hrec_cap, (size_t)ncand * (sizeof(wv::HdrRec) + 8) + 64));
-        d_flist = (uint32_t*)((char*)S.d_hrec + (size_t)ncand * sizeof(wv::HdrRec));
-        d_fflag = d_flist + ncand;
-        hipLaunchKernelGGL(ndfl_inflate_hdr_kernel, dim3((ncand + 63) / 64), dim3(64), 0, s, d_w, nwords, nbits,
-                           (const uint64_t*)S.d_cands, ncand, (wv::HdrRec*)S.d_hrec, flat_on ? d_flist : nullptr,
-                           d_nflat, flat_on ? d_fflag : nullptr);
-        INF_CHK(hipGetLastError());
-    }
-    hipLaunchKernelGGL(ndfl_inflate_order_count_kernel, dim3(otiles), dim3(SCAN_T), 0, s, (const uint64_t*)S.d_cands,
-                       ncand, end_bit, (const uint32_t*)d_rep, d_ob, flat_on ? (const uint32_t*)d_fflag : nullptr);
-    INF_CHK(hipGetLastError());
-    hipLaunchKernelGGL(ndfl_inflate_order_kernel, dim3(otiles), dim3(SCAN_T), 0, s, (const uint64_t*)S.d_cands, ncand,
-                       end_bit, d_order, (const uint32_t*)d_rep, (alias_on || flat_on) ? d_nord : (uint32_t*)nullptr, d_ob,
-                       flat_on ? (const uint32_t*)d_fflag : nullptr);
-    INF_CHK(hipGetLastError());
-    if (flat_on) INF_CHK(hipMemcpyAsync(info + LI_NFLAT, d_nflat, 4, hipMemcpyDeviceToDevice, s));
-    launch_count(s, W, ncand,
-                       d_w, nwords, nbits, (const uint64_t*)S.d_cands, (const uint64_t*)nullptr, ncand,
-                       (const uint64_t*)S.d_cands, ncand, limit, (ChainRes*)S.d_res,
-                       stats_on ? (uint32_t*)S.d_stats : nullptr, (uint64_t)0, S.pool, (uint32_t*)S.d_cticket,
-                       (wv::PhArr*)S.d_ph, (const uint32_t*)d_order, end_bit,
-                       hrec_on ? (const wv::HdrRec*)S.d_hrec : nullptr,
-                       (alias_on || flat_on) ? (const uint32_t*)d_nord : nullptr, flat_on ? (const uint32_t*)d_flist : nullptr,
-                       flat_on ? (const uint32_t*)d_nflat : nullptr);
-    INF_CHK(hipGetLastError());
-    if (alias_on) {
-        hipLaunchKernelGGL(ndfl_inflate_alias_copy_kernel, dim3(std::min<uint32_t>(1024, (ncand + 255) / 256)), dim3(256), 0, s,
-                           (const uint32_t*)d_rep, ncand, (ChainRes*)S.d_res, S.pool);
-        INF_CHK(hipGetLastError());
-    }
-    INF_CHK(hipEventRecord(S.ev[3], s));
-    if (stats_on) {                             // the count pass's chains by outcome (wave time in 10 us units)
-        std::vector<ChainRes> cr(ncand);
-        INF_CHK(hipMemcpyAsync(cr.data(), S.d_res, ncand * sizeof(ChainRes), hipMemcpyDeviceToHost, s));
-        INF_CHK(hipStreamSynchronize(s));
-        uint64_t cnt[3] = {0, 0, 0}, tsum[3] = {0, 0, 0}, tmax[3] = {0, 0, 0}, blk[3] = {0, 0, 0};
-        for (uint32_t k = 0; k < ncand; k++) {
-            const uint32_t st = std::min<uint32_t>(cr[k].status, 2u), t = cr[k].pad >> 16;
-            cnt[st]++; tsum[st] += t; tmax[st] = std::max<uint64_t>(tmax[st], t); blk[st] += cr[k].pad & 0xFFFFu;
-        }
-        if (flat_on) {
-            uint32_t fw[CT_ORDER] = {0};
-            INF_CHK(hipMemcpy(fw, S.d_cticket, sizeof(fw), hipMemcpyDeviceToHost));
-            const uint32_t* why = fw + CT_FLAT_WHY;
-            fprintf(stderr, "[ndfl] count flat groups sent back: (unused) %u, full-table tokens %u, "
-                    "error %u, chain goes on %u, table %u\n", why[1], why[2], why[3], why[4], why[5]);
-            const uint32_t nfl = fw[CT_NFLAT];
-            const unsigned long long gt = (unsigned long long)fw[CT_FLAT_TIME64] | ((unsigned long long)fw[CT_FLAT_TIME64 + 1] << 32);
-            fprintf(stderr, "[ndfl] count flat groups: %u chains in %u groups, %u sent back to the wave decode, "
-                    "group wave time %.3f ms mean\n", nfl, (nfl + 63) / 64, fw[CT_FLAT_REDO], nfl ? gt * 1e-5 / ((nfl + 63) / 64) : 0.0);
-#ifdef NDFL_FLAT_PROF
-            unsigned long long fpv[4] = {0, 0, 0, 0}, z[4] = {0, 0, 0, 0};
-            INF_CHK(hipMemcpyFromSymbol(fpv, HIP_SYMBOL(wv::g_flat_prof), 32));
-            INF_CHK(hipMemcpyToSymbol(HIP_SYMBOL(wv::g_flat_prof), z, 32));
-            fprintf(stderr, "[ndfl] flat decode loops (lane 0, clock64): %llu cycles, %llu at %llu phase points\n", fpv[0], fpv[1], fpv[2]);
-#endif
-        }
-        const char* nm[3] = {"boundary", "final", "error"};
-        for (int k = 0; k < 3; k++)
-            fprintf(stderr, "[ndfl] count chains %s: %llu, wave time %.2f ms (max %.3f ms), blocks %llu\n", nm[k],
-                    (unsigned long long)cnt[k], tsum[k] * 1e-2, tmax[k] * 1e-2, (unsigned long long)blk[k]);
-        // wave time against the chain's bits (the count order's key): per 32-Kibit bucket, and the
-        // longest chains
-        std::vector<uint64_t> cb(ncand);
-        INF_CHK(hipMemcpy(cb.data(), S.d_cands, ncand * 8, hipMemcpyDeviceToHost));
-        uint64_t bn[OB_NB] = {}, bt[OB_NB] = {}, bm[OB_NB] = {};
-        uint32_t bk[OB_NB] = {};
-        std::vector<uint32_t> top;
-        for (uint32_t k = 0; k < ncand; k++) {
-            const uint64_t nx = k + 1 < ncand ? cb[k + 1] : end_bit, len = nx > cb[k] ? nx - cb[k] : 0;
-            const uint32_t b = (uint32_t)std::min<uint64_t>(OB_NB - 1, len >> 15), t = cr[k].pad >> 16;
-            bn[b]++; bt[b] += t;
-            if (t >= bm[b]) { bm[b] = t; bk[b] = k; }
-            top.push_back(k);
-        }
-        for (uint32_t b = 0; b < OB_NB; b++)
-            if (bn[b]) fprintf(stderr, "[ndfl] count bits %2u x 32Ki: %6llu chains, mean %.3f ms, max %.3f ms "
-                               "(chain %u at bit %llu: blocks %u, status %u, out %llu)\n", b,
-                               (unsigned long long)bn[b], bt[b] * 1e-2 / bn[b], bm[b] * 1e-2, bk[b],
-                               (unsigned long long)cb[bk[b]], cr[bk[b]].pad & 0xFFFFu, cr[bk[b]].status,
-                               (unsigned long long)cr[bk[b]].out_count);
-        const size_t nt = std::min<size_t>(8, top.size());
-        std::partial_sort(top.begin(), top.begin() + nt, top.end(),
-                          [&](uint32_t a, uint32_t b) { return (cr[a].pad >> 16) > (cr[b].pad >> 16); });
-        for (size_t i = 0; i < nt; i++) {
-            const uint32_t k = top[i];
-            const uint64_t nx = k + 1 < ncand ? cb[k + 1] : end_bit;
-            fprintf(stderr, "[ndfl] count longest: chain %u at bit %llu, %llu bits, %.3f ms, blocks %u, status %u, out %llu\n",
-                    k, (unsigned long long)cb[k], (unsigned long long)(nx - cb[k]), (cr[k].pad >> 16) * 1e-2,
-                    cr[k].pad & 0xFFFFu, cr[k].status, (unsigned long long)cr[k].out_count);
-        }
-    }
-    // linking: J levels (u32), S and D double-buffered
-    uint32_t nlev = 1;
-    while ((1ull << nlev) < n) nlev++;
-    const size_t link_bytes = (size_t)(nlev + 1) * n * 4 + 2 * n * 8 + 2 * n * 4 + 64;
-    INF_CHK(inf_ensure(&S.d_link, &S.d_link_cap, link_bytes));
-    uint32_t* J = (uint32_t*)S.d_link;
-    uint64_t* Ssum[2] = {(uint64_t*)(((uintptr_t)(J + (size_t)(nlev + 1) * n) + 7) & ~(uintptr_t)7), nullptr};
-    Ssum[1] = Ssum[0] + n;
-    uint32_t* Dd[2] = {(uint32_t*)(Ssum[1] + n), nullptr};
-    Dd[1] = Dd[0] + n;
-    const uint32_t lg = (uint32_t)std::min<uint64_t>(4096, (n + 255) / 256);
-    hipLaunchKernelGGL(ndfl_inflate_link_init_kernel, dim3(lg), dim3(256), 0, s, (const ChainRes*)S.d_res, ncand,
-                       (const uint64_t*)S.d_cands, end_bit, J, Ssum[0], Dd[0]);
-    INF_CHK(hipGetLastError());
-    int cur = 0;
-    for (uint32_t r = 0; r < nlev; r++) {
-        hipLaunchKernelGGL(ndfl_inflate_link_jump_kernel, dim3(lg), dim3(256), 0, s, (const uint32_t*)(J + (size_t)r * n),
-                           J + (size_t)(r + 1) * n, (const uint64_t*)Ssum[cur], Ssum[cur ^ 1], (const uint32_t*)Dd[cur],
-                           Dd[cur ^ 1], ncand);
-        INF_CHK(hipGetLastError());
-        cur ^= 1;
-    }
-    INF_CHK(inf_ensure(&S.d_chains, &S.d_chains_cap, n * sizeof(EmitChain)));
-    hipLaunchKernelGGL(ndfl_inflate_link_path_kernel, dim3(lg), dim3(256), 0, s, (const uint32_t*)J, nlev,
-                       (const uint64_t*)Ssum[cur], (const uint32_t*)Dd[cur], (const ChainRes*)S.d_res,
-                       (const uint64_t*)S.d_cands, ncand, dict_len, end_bit, out_cap, (EmitChain*)S.d_chains, info);
-    INF_CHK(hipGetLastError());
-    // the emit pass claims the linked chains costliest first (the count pass's order buffer is free)
-    {
-        uint32_t* d_eob = (uint32_t*)S.d_cticket + CT_ORDER + OB_WORDS;     // emit order: tot, cursor (zeroed above)
-        const uint32_t etiles = (ncand + SCAN_TILE - 1) / SCAN_TILE;    // (chains <= candidates)
-        hipLaunchKernelGGL(ndfl_inflate_emit_order_count_kernel, dim3(etiles), dim3(SCAN_T), 0, s,
-                           (const EmitChain*)S.d_chains, (const uint64_t*)info, d_eob);
-        INF_CHK(hipGetLastError());
-        hipLaunchKernelGGL(ndfl_inflate_emit_order_kernel, dim3(etiles), dim3(SCAN_T), 0, s, (const EmitChain*)S.d_chains,
-                           (const uint64_t*)info, d_order, d_eob);
-        INF_CHK(hipGetLastError());
-    }
-    // emit into the output (or a device staging buffer sized by the bound out_cap)
-    uint8_t* d_out;
-    const bool direct = (flags & 2u) != 0;
-    // the output's size is known on the device only: the scratch (back-references, pending bits,
-    // a staging copy) is sized by out_cap, capped at DEFLATE's largest expansion (258 bytes per 2 bits)
-    const uint64_t obytes = dict_len + std::min<uint64_t>(out_cap, 129 * nbits + 65536);
-    if (obytes > (40ull << 30)) return LINK_FALLBACK;          // (the host path sizes it exactly)
-    if (direct) d_out = out;
-    else {
-        INF_CHK(inf_ensure(&S.d_out, &S.d_out_cap, obytes + 64));
-        d_out = (uint8_t*)S.d_out;
-        if (dict_len) INF_CHK(hipMemcpyAsync(d_out, out, dict_len, hipMemcpyHostToDevice, s));
-    }
-    const uint64_t nbytes = obytes;
-    if ((nbytes + 31) / 32 > 0xFFFFFFFFull) return LINK_FALLBACK;
-    const uint64_t npw = (nbytes + 31) / 32;
-    INF_CHK(inf_ensure(&S.d_ref, &S.d_ref_cap, nbytes * 4 + 64));
-    INF_CHK(inf_ensure(&S.d_pend, &S.d_pend_cap, npw * 4 + 64));
-    INF_CHK(hipMemsetAsync(S.d_pend, 0, npw * 4 + 64, s));
-    if (!S.d_ticket) INF_CHK(hipMalloc(&S.d_ticket, 64));
-    INF_CHK(hipMemsetAsync(S.d_ticket, 0, 64, s));
-    if (S.knobs.test_segflip && S.pool.cnt) {         // (test: record 0, lane 0 counts one byte more)
-        uint32_t c0 = 0;
-        INF_CHK(hipMemcpyAsync(&c0, S.pool.cnt, 4, hipMemcpyDeviceToHost, s));
-        INF_CHK(hipStreamSynchronize(s));
-        c0++;
-        INF_CHK(hipMemcpyAsync(S.pool.cnt, &c0, 4, hipMemcpyHostToDevice, s));
-        INF_CHK(hipStreamSynchronize(s));
-    }
-    INF_CHK(hipEventRecord(S.ev[4], s));
-    static const uint32_t emit_grid = wave_grid(ndfl_inflate_emit_wave_kernel, EMIT_WAVES, "NDFL_EMIT_WPC");
-    // the record-replay emit kernel first, the full one over what it leaves (NDFL_EMIT_FAST=0: the
-    // full one alone)
-    if (S.knobs.emit_fast) {
-        INF_CHK(inf_ensure(&S.d_slow, &S.d_slow_cap, (size_t)ncand * 4 + 64));
-        uint32_t* tk = (uint32_t*)S.d_ticket;             // [0] fast tickets, [4] full tickets, [8] slow count
-        static const uint32_t fast_grid = wave_grid(ndfl_inflate_emit_fast_kernel, EMIT_WAVES, "NDFL_EMITF_WPC");
-        hipLaunchKernelGGL(ndfl_inflate_emit_fast_kernel, dim3(std::min<uint32_t>(ncand, fast_grid)), dim3(64), 0, s, d_w,
-                           nwords, nbits, (const EmitChain*)S.d_chains, tk, d_out, (ChainRes*)S.d_res,
-                           (uint32_t*)S.d_ref, (uint32_t*)S.d_pend, S.pool, (const uint64_t*)info, (const uint32_t*)d_order,
-                           (uint32_t*)S.d_slow, tk + 8);
-        INF_CHK(hipGetLastError());
-        hipLaunchKernelGGL(ndfl_inflate_emit_wave_kernel, dim3(std::min<uint32_t>(ncand, emit_grid)), dim3(64), 0, s, d_w,
-                           nwords, nbits, (const EmitChain*)S.d_chains, ncand, tk + 4, d_out,
-                           (ChainRes*)S.d_res, (const uint64_t*)S.d_cands, ncand, (uint32_t*)S.d_ref, (uint32_t*)S.d_pend,
-                           S.pool, (wv::PhArr*)S.d_ph, stats_on ? (uint32_t*)S.d_stats : nullptr, (const uint64_t*)info,
-                           (const uint32_t*)S.d_slow, (const uint32_t*)(tk + 8));
-        INF_CHK(hipGetLastError());
-        if (stats_on) {
-            uint32_t nsl = 0;
-            INF_CHK(hipMemcpyAsync(&nsl, tk + 8, 4, hipMemcpyDeviceToHost, s));
-            INF_CHK(hipStreamSynchronize(s));
-            fprintf(stderr, "[ndfl] fast emit pass left %u chains to the full emit pass\n", nsl);
-        }
-    } else {
-        hipLaunchKernelGGL(ndfl_inflate_emit_wave_kernel, dim3(std::min<uint32_t>(ncand, emit_grid)), dim3(64), 0, s, d_w,
-                           nwords, nbits, (const EmitChain*)S.d_chains, ncand, (uint32_t*)S.d_ticket, d_out,
-                           (ChainRes*)S.d_res, (const uint64_t*)S.d_cands, ncand, (uint32_t*)S.d_ref, (uint32_t*)S.d_pend,
-                           S.pool, (wv::PhArr*)S.d_ph, stats_on ? (uint32_t*)S.d_stats : nullptr, (const uint64_t*)info,
-                           (const uint32_t*)d_order, (const uint32_t*)nullptr);
-        INF_CHK(hipGetLastError());
-    }
-    INF_CHK(hipEventRecord(S.ev[5], s));
-    {
-        uint32_t* d_first = (uint32_t*)S.d_cticket + CT_ORDER + 2 * OB_WORDS;
-        INF_CHK(hipMemsetAsync(d_first, 0xFF, 4, s));
-        hipLaunchKernelGGL(ndfl_inflate_first_error_kernel, dim3((ncand + SCAN_TILE - 1) / SCAN_TILE), dim3(SCAN_T), 0, s,
-                           (const ChainRes*)S.d_res, (const uint64_t*)info, d_first);
-        INF_CHK(hipGetLastError());
-        hipLaunchKernelGGL(ndfl_inflate_summary_kernel, dim3(1), dim3(64), 0, s, (const ChainRes*)S.d_res,
-                           (const EmitChain*)S.d_chains, info, dict_len, partial ? 1u : 0u, (const uint32_t*)d_first);
-        INF_CHK(hipGetLastError());
-    }
-    // the resolve rounds, as far as they usually go, without a host read in between
-    uint32_t* left = nullptr;
-    if (!deferred) {
-        rc = resolve_rounds_dev(S, s, d_out, nbytes, 6, &left, stats_on ? info + LI_WORDS - 3 : (uint64_t*)nullptr);
-        if (rc) return rc;
-        if (left) INF_CHK(hipMemcpyAsync(info + LI_WORDS - 1, left, 4, hipMemcpyDeviceToDevice, s));
-    }
-    INF_CHK(hipMemcpyAsync((void*)hinfo, info, LI_WORDS * 8, hipMemcpyDeviceToHost, s));
-    INF_CHK(hipStreamSynchronize(s));                          // (2) the summary
-    if (stats_on) {
-        uint32_t st[3] = {0, 0, 0};
-        INF_CHK(hipMemcpy(st, S.d_stats, sizeof(st), hipMemcpyDeviceToHost));
-        fprintf(stderr, "[ndfl] device link: chains %llu of %u candidates; count pass: slow-verify lanes %u fixups %u "
-                "rounds %u\n", (unsigned long long)hinfo[LI_NCH], ncand, st[SW_NSLOW], st[SW_NFIX], st[SW_NROUND]);
-        fprintf(stderr, "[ndfl] emit: %u pending 32-byte groups before the resolve rounds, %u after six\n",
-                (uint32_t)(hinfo[LI_WORDS - 3] & 0xFFFFFFFFu), (uint32_t)(hinfo[LI_WORDS - 1] & 0xFFFFFFFFu));
-        rc = print_count_stats(S, true);
-        if (rc) return rc;
-    }
-    const uint64_t lflags = hinfo[LI_FLAGS];
-    if (lflags & LF_REPAIR) return LINK_FALLBACK;
-    if (lflags & LF_RANGE) return -1;                          // the range end is no block boundary
-    S.chains = hinfo[LI_NCH];
-    S.candidates = ncand;
-    S.flat_chains = hinfo[LI_NFLAT];
-    S.repairs = 0;
-    if (lflags & LF_CAPACITY) { *out_len = hinfo[LI_TOTAL]; return -3; }
-    const uint32_t pending_left = (uint32_t)(hinfo[LI_WORDS - 1] & 0xFFFFFFFFu);
-    S.pending_after_dev = deferred ? 0 : pending_left;
-    if (!deferred && pending_left) {
-        uint64_t groups = 0;
-        rc = resolve_rounds(S, s, d_out, nbytes, &groups);     // (the rest, with the host's checks)
-        if (rc) return rc;
-    }
-    {
-        float a = 0, b = 0, c = 0;
-        hipEventElapsedTime(&a, S.ev[0], S.ev[1]);
-        hipEventElapsedTime(&b, S.ev[2], S.ev[3]);
-        hipEventElapsedTime(&c, S.ev[4], S.ev[5]);
-        S.last_ms_find = a; S.last_ms_count = b; S.last_ms_emit = c;
-    }
-    if (deferred) { S.pending = true; S.p_out = d_out; S.p_nbytes = dict_len + hinfo[LI_TOTAL]; S.p_dict_len = dict_len; }
-    INF_CHK(hipEventRecord(S.ev[5], s));
-    INF_CHK(hipStreamSynchronize(s));
-    float w = 0;
-    hipEventElapsedTime(&w, S.ev[0], S.ev[5]);
-    S.last_ms_wall = w;
-    *last_ms = w;
-    const int code = (int)hinfo[LI_CODE];
-    const uint64_t produced = hinfo[LI_OUTLEN];
-    if (!direct && produced) INF_CHK(hipMemcpy(out + dict_len, d_out + dict_len, produced, hipMemcpyDeviceToHost));
-    *out_len = produced;
-    *consumed_bits = hinfo[LI_CONSUMED];
-    return code;
-}
-
-// The decoder's input words: staged into a zero-padded scratch copy, so the decode lanes' 16-byte
-// prefetches (up to IN_PAD bytes past the end) need no bounds checks -- unless the caller says its
-// device buffer already is one (NDFL_IN_PADDED: 16-byte aligned, IN_PAD zero bytes after the data),
-// in which case it is read in place.
-static int stage_input(InflateScratch& S, hipStream_t s, const uint8_t* in, uint64_t in_len, uint32_t flags,
-                       const uint32_t** d_w) {
-    using namespace inf;
-    const uint64_t nwords = (in_len + 3) / 4;
-    const bool in_place = in_len && (flags & 1u) && (flags & 8u) && ((uintptr_t)in & 15u) == 0;
-    *d_w = (const uint32_t*)in;
-    if (!in_place) {
-        INF_CHK(inf_ensure(&S.d_in, &S.d_in_cap, nwords * 4 + IN_PAD));
-        if (in_len) INF_CHK(hipMemcpyAsync(S.d_in, in, in_len, (flags & 1u) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-        INF_CHK(hipMemsetAsync((char*)S.d_in + in_len, 0, nwords * 4 + IN_PAD - in_len, s));
-        *d_w = (const uint32_t*)S.d_in;
-    }
-    return 0;
-}
-
-// The header finder phase: every bit position of [start_bit, min(end_bit, nbits)) tested for a
-// block header (finder: cheap masks + the code-length code's Kraft test), the survivors checked by
-// the reference's own header rules (strict stage), the accepted ones into the per-segment lists
-// d_list / d_cnt (SEG_BYTES of input each).  S.d_stats and d_cnt must be zeroed.
-static int find_headers(InflateScratch& S, hipStream_t s, const uint32_t* d_w, uint64_t nwords, uint64_t nbits,
-                        uint64_t start_bit, uint64_t end_bit, uint32_t* d_cnt, uint64_t* d_list) {
-    using namespace inf;
-    // only the range's own bits are scanned: candidates outside [start_bit, end_bit) are dropped
-    // later anyway (a range decode of one stream shard, or a sync probe)
-    const uint64_t scan_end = std::min(end_bit, nbits);
-    const uint64_t w_lo = start_bit >> 5;
-    const uint64_t nw32 = scan_end > w_lo * 32 ? (scan_end + 31) / 32 - w_lo : 0;
-    // The survivor list: nbits / 256 + 64 K entries (about one survivor per 1,000 positions on real
-    // streams).  A scan whose survivors overflowed it is run again with room for all of them
-    // (FIND_OVERFLOW, q_min), up to Q_BUDGET entries (1 GiB of list): periodic stored data can pass
-    // the filters every ~32 bits, and a 4 GiB stream of it would ask for 8 GiB.  Past the budget, or
-    // when the allocation fails, the decode goes on with the list it has (q_full): a survivor past
-    // the list is a chain start not taken -- the chain before it decodes through that block -- so it
-    // costs parallelism, never a result.
-    constexpr uint64_t Q_BUDGET = (1ull << 30) / 8;
-    const uint64_t qbase = std::min<uint64_t>(0x7FFFFFFFull, nbits / 256 + 65536);
-    const uint64_t qtop = std::min<uint64_t>(0x7FFFFFFFull, std::max(qbase, Q_BUDGET));
-    uint32_t qcap = (uint32_t)std::max(qbase, std::min<uint64_t>(S.q_min, qtop));
-    S.q_full = qcap >= qtop;
-    if (inf_ensure(&S.d_q, &S.d_q_cap, (uint64_t)qcap * 8 + 64) != hipSuccess) {
-        (void)hipGetLastError();                     // (an out-of-memory result is not a sticky error)
-        qcap = (uint32_t)qbase;
-        S.q_full = true;
-        S.q_min = 0;
-        INF_CHK(inf_ensure(&S.d_q, &S.d_q_cap, (uint64_t)qcap * 8 + 64));
-    }
-    S.q_cap = qcap;
-    uint32_t* d_qcount = (uint32_t*)S.d_stats + SW_QCOUNT;
-    uint64_t* d_qlist = (uint64_t*)((char*)S.d_q + 64);
-    static const uint32_t strict_grid = [] {
-        int dev = 0, ncu = 0, per = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, ndfl_inflate_strict_kernel, 256, 0) != hipSuccess ||
-            ncu <= 0 || per <= 0)
-            return 1280u;
-        return (uint32_t)(ncu * per);
-    }();
-    unsigned long long* sst = S.knobs.stats ? (unsigned long long*)((uint32_t*)S.d_stats + SW_STRICT64) : nullptr;
-    if (nw32) {
-        const uint32_t fgrid = (uint32_t)((nw32 + 256 * FIND_WPT - 1) / (256 * FIND_WPT));
-        hipLaunchKernelGGL(ndfl_inflate_find_compact_kernel, dim3(fgrid), dim3(256), 0, s, d_w, nwords, nbits, d_qlist,
-                           d_qcount, qcap, w_lo, scan_end);
-        INF_CHK(hipGetLastError());
-        hipLaunchKernelGGL(ndfl_inflate_strict_kernel, dim3(strict_grid), dim3(256), 0, s, d_w, nwords, nbits,
-                           (const uint64_t*)d_qlist, (const uint32_t*)d_qcount, qcap, d_cnt, d_list,
-                           (uint32_t*)S.d_stats + SW_STRICT_TICKET, sst);
-        INF_CHK(hipGetLastError());
-    }
-    return 0;
-}
-
-// Diagnostics (ndfl_inflate_headers): the finder phase alone over a whole stream.  out = the accepted
-// headers in ascending order (the per-segment lists, each capped at SEG_CAP, as the decode sees
-// them); surv = the finder's survivors (unsorted, bit 63 = dynamic); stats[0] survivors found,
-// [1] headers accepted before the cap, [2] segments over SEG_CAP, [3] survivors past the list's
-// capacity (dropped).
-static int inflate_headers(InflateScratch& S, hipStream_t s, const uint8_t* in, uint64_t in_len, uint32_t flags,
-                           uint64_t* out, uint64_t cap, uint64_t* n_out, uint64_t* surv, uint64_t surv_cap,
-                           uint64_t* stats) {
-    using namespace inf;
-    const uint64_t nbits = in_len * 8, nwords = (in_len + 3) / 4;
-    const uint32_t* d_w = nullptr;
-    INF_RC(stage_input(S, s, in, in_len, flags, &d_w));
-    if (!S.d_stats) INF_CHK(hipMalloc(&S.d_stats, 512));
-    const uint32_t nseg = (uint32_t)std::max<uint64_t>(1, (in_len + SEG_BYTES - 1) / SEG_BYTES);
-    INF_CHK(inf_ensure(&S.d_cand, &S.d_cand_cap, (uint64_t)nseg * SEG_CAP * 8ull + (uint64_t)nseg * 4 + 64));
-    uint64_t* d_list = (uint64_t*)S.d_cand;
-    uint32_t* d_cnt = (uint32_t*)((char*)S.d_cand + (uint64_t)nseg * SEG_CAP * 8ull);
-    std::vector<uint32_t> cnt(nseg);
-    std::vector<uint64_t> lists((uint64_t)nseg * SEG_CAP);
-    uint32_t qc = 0;
-    for (int finds = 0; finds < 2; finds++) {                   // (as inflate_run: FIND_OVERFLOW scans again)
-        INF_CHK(hipMemsetAsync(S.d_stats, 0, 512, s));
-        INF_CHK(hipMemsetAsync(d_cnt, 0, (uint64_t)nseg * 4, s));
-        INF_RC(find_headers(S, s, d_w, nwords, nbits, 0, NONE, d_cnt, d_list));
-        INF_CHK(hipMemcpyAsync(&qc, (uint32_t*)S.d_stats + SW_QCOUNT, 4, hipMemcpyDeviceToHost, s));
-        INF_CHK(hipStreamSynchronize(s));
-        if (qc <= S.q_cap || S.q_full) break;
-        S.q_min = qc + 65536;
-    }
-    INF_CHK(hipMemcpyAsync(cnt.data(), d_cnt, nseg * 4ull, hipMemcpyDeviceToHost, s));
-    INF_CHK(hipMemcpyAsync(lists.data(), d_list, lists.size() * 8, hipMemcpyDeviceToHost, s));
-    INF_CHK(hipStreamSynchronize(s));
-    const uint32_t qcap = S.q_cap;
-    std::vector<uint64_t> acc;
-    uint64_t total = 0, over = 0;
-    for (uint32_t k = 0; k < nseg; k++) {
-        total += cnt[k];
-        over += cnt[k] > SEG_CAP;
-        for (uint32_t i = 0; i < std::min(cnt[k], SEG_CAP); i++) acc.push_back(lists[(uint64_t)k * SEG_CAP + i]);
-    }
-    std::sort(acc.begin(), acc.end());
-    *n_out = acc.size();
-    if (out) memcpy(out, acc.data(), std::min<uint64_t>(cap, acc.size()) * 8);
-    if (surv && surv_cap) {
-        const uint64_t ns = std::min<uint64_t>(std::min<uint64_t>(qc, qcap), surv_cap);
-        if (ns) INF_CHK(hipMemcpy(surv, (const char*)S.d_q + 64, ns * 8, hipMemcpyDeviceToHost));
-    }
-    if (stats) { stats[0] = qc; stats[1] = total; stats[2] = over; stats[3] = qc > qcap ? qc - qcap : 0; }
-    return 0;
-}
-
-// Decode one raw DEFLATE stream, or the block-aligned range [start_bit, end_bit) of one.
-//   out       the window start: out[0, dict_len) holds the dict_len bytes of output preceding the
-//             range (0 for a whole stream); decoded bytes go to out[dict_len, dict_len + n)
-//   deferred  the window content is not valid yet: chains that read it (directly or through other
-//             chains) are recorded and re-emitted by inflate_resolve once it is written
-static int inflate_run(InflateScratch& S, hipStream_t s, const uint8_t* in, uint64_t in_len, uint64_t start_bit,
-                       uint64_t end_bit, uint8_t* out, uint64_t dict_len, uint64_t out_cap, uint64_t* out_len,
-                       uint64_t* consumed_bits, uint32_t flags, bool deferred, double* last_ms, bool partial = false,
-                       uint64_t* probe_sync = nullptr) {
-    using namespace inf;
-    *out_len = 0;
-    *consumed_bits = 0;
-    S.pending = false;
-    if (!probe_sync) S.pending_after_dev = 0;
-    const bool htime = S.knobs.host_times;
-    auto hnow = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double ht[8] = {hnow(), 0, 0, 0, 0, 0, 0, 0};
-    const uint64_t nbits = in_len * 8;
-    const uint64_t nwords = (in_len + 3) / 4;
-    if (start_bit > nbits) return -1;
-    const uint32_t* d_w = nullptr;
-    INF_RC(stage_input(S, s, in, in_len, flags, &d_w));
-    if (!S.d_stats) INF_CHK(hipMalloc(&S.d_stats, 512));
-    if (!S.ev[0]) for (auto& e : S.ev) INF_CHK(hipEventCreate(&e));
-    int finds = 0;
-refind:
-    INF_CHK(hipMemsetAsync(S.d_stats, 0, 512, s));
-    const uint32_t nseg = (uint32_t)std::max<uint64_t>(1, (in_len + SEG_BYTES - 1) / SEG_BYTES);
-    INF_CHK(inf_ensure(&S.d_cand, &S.d_cand_cap, (uint64_t)nseg * SEG_CAP * 8ull + (uint64_t)nseg * 4 + 64));
-    uint64_t* d_list = (uint64_t*)S.d_cand;
-    uint32_t* d_cnt = (uint32_t*)((char*)S.d_cand + (uint64_t)nseg * SEG_CAP * 8ull);
-    INF_CHK(hipMemsetAsync(d_cnt, 0, (uint64_t)nseg * 4, s));
-    INF_CHK(hipEventRecord(S.ev[0], s));
-    INF_RC(find_headers(S, s, d_w, nwords, nbits, start_bit, end_bit, d_cnt, d_list));
-    INF_CHK(hipEventRecord(S.ev[1], s));
-    // the device-side path (NDFL_HOST_LINK selects the host's linking); sync probes keep the host's
-    {
-        const bool host_link = S.knobs.host_link;
-        if (!probe_sync && !host_link) {
-            const int rc = inflate_devlink(S, s, d_w, nwords, nbits, nseg, d_cnt, d_list, start_bit, end_bit, out,
-                                           dict_len, out_cap, out_len, consumed_bits, flags, deferred, partial, last_ms);
-            if (rc == FIND_OVERFLOW && finds++ == 0) goto refind;
-            if (rc != LINK_FALLBACK && rc != FIND_OVERFLOW) return rc;
-        }
-    }
-    std::vector<uint32_t> hcnt(nseg);
-    uint32_t hqc = 0;
-    INF_CHK(hipMemcpyAsync(hcnt.data(), d_cnt, nseg * 4ull, hipMemcpyDeviceToHost, s));
-    INF_CHK(hipMemcpyAsync(&hqc, (const uint32_t*)S.d_stats + SW_QCOUNT, 4, hipMemcpyDeviceToHost, s));
-    INF_CHK(hipStreamSynchronize(s));
-    if (hqc > S.q_cap && !S.q_full && finds++ == 0) { S.q_min = hqc + 65536; goto refind; }
-    std::vector<uint64_t> hoff(nseg + 1);
-    hoff[0] = 1;                                   // slot 0 is the range start
-    for (uint32_t k = 0; k < nseg; k++) hoff[k + 1] = hoff[k] + std::min(hcnt[k], SEG_CAP);
-    const uint64_t ncand_all = hoff[nseg];
-    INF_CHK(inf_ensure(&S.d_starts, &S.d_starts_cap, (ncand_all + nseg + 2) * 8));
-    uint64_t* d_sorted = (uint64_t*)S.d_starts;
-    uint64_t* d_segoff = d_sorted + ncand_all;
-    INF_CHK(hipMemcpyAsync(d_segoff, hoff.data(), nseg * 8ull, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(ndfl_inflate_compact_kernel, dim3((nseg + 3) / 4), dim3(256), 0, s, (const uint32_t*)d_cnt,
-                       (const uint64_t*)d_list, (const uint64_t*)d_segoff, nseg, d_sorted);
-    INF_CHK(hipGetLastError());
-    std::vector<uint64_t> starts(ncand_all);
-    INF_CHK(hipMemcpyAsync(starts.data() + 1, d_sorted + 1, (ncand_all - 1) * 8, hipMemcpyDeviceToHost, s));
-    INF_CHK(hipStreamSynchronize(s));
-    starts[0] = start_bit;
-    // keep candidates inside the range; drop a duplicate of the start (a header found there)
-    {
-        size_t m = 1;
-        for (size_t k = 1; k < starts.size(); k++)
-            if (starts[k] > start_bit && starts[k] < end_bit) starts[m++] = starts[k];
-        starts.resize(m);
-    }
-    const std::vector<uint64_t> sorted_cand(starts);
-    // the sorted candidate list on the device: the wave passes split block data at the next one
-    const uint32_t ncand = (uint32_t)sorted_cand.size();
-    INF_CHK(inf_ensure(&S.d_cands, &S.d_cands_cap, (ncand + 1) * 8ull));
-    INF_CHK(hipMemcpyAsync(S.d_cands, sorted_cand.data(), ncand * 8ull, hipMemcpyHostToDevice, s));
-    const uint64_t limit = std::min(end_bit, nbits);
-    // segment records: one head per counted chain start (index in `starts`)
-    {
-        const int prc = setup_pool(S, s, starts.size(), nbits);
-        if (prc) return prc;
-    }
-    const SegPool pool = S.pool;
-
-    const bool stats_on = S.knobs.stats;
-    std::vector<ChainRes> res;
-    auto run_count = [&](const std::vector<uint64_t>& st, std::vector<ChainRes>& r) -> int {
-        const uint64_t slot_base = starts.size() - (&st == &starts ? st.size() : 0);
-        const size_t n = st.size();
-        std::vector<uint64_t> sp(n);
-        for (size_t k = 0; k < n; k++) sp[k] = end_bit;     // chains stop at exact candidates (kernel)
-        // claim order: longest first (by the bits to the next start), so that no long chain is
-        // left for the end of the launch; bucketed by 32 Kibit
-        std::vector<uint32_t> order(n);
-        {
-            constexpr int NB = 24;
-            uint32_t bc[NB + 1] = {0};
-            auto bucket = [&](size_t k) {
-                const uint64_t nx = k + 1 < n ? st[k + 1] : end_bit;
-                const uint64_t len = nx > st[k] ? nx - st[k] : 0;
-                return NB - 1 - (int)std::min<uint64_t>(NB - 1, len >> 15);
-            };
-            const bool sorted_st = std::is_sorted(st.begin(), st.end());
-            if (sorted_st) {
-                for (size_t k = 0; k < n; k++) bc[bucket(k) + 1]++;
-                for (int b = 0; b < NB; b++) bc[b + 1] += bc[b];
-                for (size_t k = 0; k < n; k++) order[bc[bucket(k)]++] = (uint32_t)k;
-            } else {
-                for (size_t k = 0; k < n; k++) order[k] = (uint32_t)k;
-            }
-        }
-        INF_CHK(inf_ensure(&S.d_starts, &S.d_starts_cap, n * 8));
-        INF_CHK(inf_ensure(&S.d_stops, &S.d_stops_cap, n * 12));
-        INF_CHK(inf_ensure(&S.d_res, &S.d_res_cap, n * sizeof(ChainRes)));
-        INF_CHK(hipMemcpyAsync(S.d_starts, st.data(), n * 8, hipMemcpyHostToDevice, s));
-        INF_CHK(hipMemcpyAsync(S.d_stops, sp.data(), n * 8, hipMemcpyHostToDevice, s));
-        uint32_t* d_order = (uint32_t*)((char*)S.d_stops + n * 8);
-        INF_CHK(hipMemcpyAsync(d_order, order.data(), n * 4, hipMemcpyHostToDevice, s));
-        if (!S.d_ph) INF_CHK(hipMalloc(&S.d_ph, (size_t)std::max(COUNT_WAVES, EMIT_WAVES) * sizeof(wv::PhArr)));
-        if (!S.d_cticket) INF_CHK(hipMalloc(&S.d_cticket, CTK_BYTES));
-        INF_CHK(hipMemsetAsync(S.d_cticket, 0, 4, s));
-        if (S.count_first) INF_CHK(hipEventRecord(S.ev[2], s));
-        launch_count(s, count_w(S.knobs), (uint32_t)n,
-                           d_w, nwords, nbits,
-                           (const uint64_t*)S.d_starts, (const uint64_t*)S.d_stops, (uint32_t)n,
-                           (const uint64_t*)S.d_cands, ncand, limit, (ChainRes*)S.d_res, stats_on ? (uint32_t*)S.d_stats : nullptr,
-                           slot_base, pool, (uint32_t*)S.d_cticket, (wv::PhArr*)S.d_ph, (const uint32_t*)d_order,
-                           end_bit, (const wv::HdrRec*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr,
-                           (const uint32_t*)nullptr);
-        INF_CHK(hipGetLastError());
-        if (S.count_first) { INF_CHK(hipEventRecord(S.ev[3], s)); S.count_first = false; }
-        r.resize(n);
-        INF_CHK(hipMemcpyAsync(r.data(), S.d_res, n * sizeof(ChainRes), hipMemcpyDeviceToHost, s));
-        INF_CHK(hipStreamSynchronize(s));
-        return 0;
-    };
-    ht[1] = hnow();
-    S.repairs = 0;
-    S.count_first = true;
-    int rc = run_count(starts, res);
-    if (rc) return rc;
-    if (probe_sync) {
-        // sync probe: a chain of blocks from a header candidate that ends exactly at another
-        // candidate y has decoded up to y in step with the stream (a decode that starts off a block
-        // boundary re-synchronises inside the block and then ends at its real end-of-block), so y
-        // is a block boundary; y is taken when its own chain links on in turn (or is final)
-        *probe_sync = NONE;
-        auto linked = [&](size_t k) {
-            return res[k].status == ST_BOUNDARY && res[k].next < starts.size() && starts[res[k].next] == res[k].end_bit;
-        };
-        for (size_t k = 1; k < res.size(); k++) {
-            if (!linked(k)) continue;
-            const size_t j = res[k].next;
-            if (j >= 1 && (linked(j) || res[j].status == ST_FINAL)) { *probe_sync = starts[j]; break; }
-        }
-        return 0;
-    }
-    if (S.knobs.stats && !probe_sync) {
-        // the most expensive chains (wave time, blocks, bits, output bytes)
-        std::vector<size_t> idx(res.size());
-        for (size_t k = 0; k < idx.size(); k++) idx[k] = k;
-        const size_t top = std::min<size_t>(8, idx.size());
-        std::partial_sort(idx.begin(), idx.begin() + top, idx.end(),
-                          [&](size_t a, size_t b) { return (res[a].pad >> 16) > (res[b].pad >> 16); });
-        for (size_t t = 0; t < top; t++) {
-            const ChainRes& r = res[idx[t]];
-            fprintf(stderr, "[ndfl] count chain %zu: %.2f ms, %u blocks, start %llu, %llu bits, %llu bytes, status %u\n",
-                    idx[t], (r.pad >> 16) * 0.01, r.pad & 0xFFFFu, (unsigned long long)starts[idx[t]],
-                    (unsigned long long)(r.end_bit - starts[idx[t]]), (unsigned long long)r.out_count, r.status);
-        }
-    }
-    {
-        float a = 0, b = 0;
-        hipEventElapsedTime(&a, S.ev[0], S.ev[1]);
-        hipEventElapsedTime(&b, S.ev[2], S.ev[3]);
-        S.last_ms_find = a; S.last_ms_count = b;
-    }
-
-    // link from the range start.  A boundary that is no candidate (fixed-Huffman block, header
-    // rejected by the finder) is repaired: every such boundary of every chain is decoded on in
-    // parallel rounds; a final serial fallback guarantees progress.
-    // chain starts: the sorted candidate prefix (binary search) plus repaired boundaries
-    const size_t n0 = starts.size();
-    std::unordered_map<uint64_t, size_t> extra;
-    auto find_at = [&](uint64_t b, size_t& idx) -> bool {
-        auto it = std::lower_bound(starts.begin(), starts.begin() + n0, b);
-        if (it != starts.begin() + n0 && *it == b) { idx = (size_t)(it - starts.begin()); return true; }
-        auto e = extra.find(b);
-        if (e != extra.end()) { idx = e->second; return true; }
-        return false;
-    };
-    for (int round = 0; round < 8; round++) {
-        std::vector<uint64_t> todo;
-        size_t dummy;
-        for (size_t k = 0; k < res.size(); k++)
-            if (res[k].status == ST_BOUNDARY && res[k].end_bit < end_bit &&
-                !(res[k].next < n0 && starts[res[k].next] == res[k].end_bit) && !find_at(res[k].end_bit, dummy)) {
-                extra[res[k].end_bit] = NONE;       // placeholder, filled below
-                todo.push_back(res[k].end_bit);
-            }
-        if (todo.empty()) break;
-        std::vector<ChainRes> r2;
-        rc = run_count(todo, r2);
-        if (rc) return rc;
-        for (size_t k = 0; k < todo.size(); k++) {
-            starts.push_back(todo[k]);
-            res.push_back(r2[k]);
-            extra[todo[k]] = starts.size() - 1;
-        }
-        S.repairs += todo.size();
-    }
-    ht[2] = hnow();
-    std::vector<EmitChain> chains;
-    std::vector<uint64_t> offs;
-    uint64_t off = dict_len;
-    size_t cur = 0;
-    uint64_t stop_bit = 0;
-    for (;;) {
-        const ChainRes& r = res[cur];
-        EmitChain ec;
-        ec.start_bit = starts[cur];
-        ec.end_bit = r.end_bit;
-        ec.out_off = off;
-        ec.out_count = r.out_count;
-        ec.slot = cur;
-        chains.push_back(ec);
-        offs.push_back(off);
-        off += r.out_count;
-        if (r.status == ST_FINAL) { stop_bit = r.end_bit; break; }
-        if (r.status == ST_ERROR) break;
-        if (r.end_bit == end_bit) { stop_bit = end_bit; break; }
-        if (r.end_bit > end_bit) return -1;          // the range end is no block boundary
-        size_t nxt;
-        if (r.next < n0 && starts[r.next] == r.end_bit) { cur = r.next; continue; }
-        if (find_at(r.end_bit, nxt) && nxt != (size_t)NONE) { cur = nxt; continue; }
-        // serial fallback (beyond the parallel rounds)
-        std::vector<uint64_t> st1{r.end_bit};
-        std::vector<ChainRes> r1;
-        rc = run_count(st1, r1);
-        if (rc) return rc;
-        starts.push_back(r.end_bit);
-        res.push_back(r1[0]);
-        extra[r.end_bit] = starts.size() - 1;
-        cur = starts.size() - 1;
-        S.repairs++;
-    }
-    S.chains = chains.size();
-    S.flat_chains = 0;
-    S.candidates = sorted_cand.size();
-    if (S.knobs.stats) {
-        uint32_t st[SW_QCOUNT + 1] = {0};
-        INF_CHK(hipMemcpy(st, S.d_stats, sizeof(st), hipMemcpyDeviceToHost));
-        fprintf(stderr, "[ndfl] finder quick survivors %u; count pass: chains %zu candidates %zu repairs %llu "
-                "slow-verify lanes %u fixups %u rounds %u\n", st[SW_QCOUNT], chains.size(), sorted_cand.size(),
-                (unsigned long long)S.repairs, st[SW_NSLOW], st[SW_NFIX], st[SW_NROUND]);
-        const int prc = print_count_stats(S, false);
-        if (prc) return prc;
-    }
-    const uint64_t total = off - dict_len;
-    ht[3] = hnow();
-    if (total > out_cap) { *out_len = total; return -3; }
-
-    // emit pass
-    const uint32_t nch = (uint32_t)chains.size();
-    INF_CHK(inf_ensure(&S.d_chains, &S.d_chains_cap, nch * sizeof(EmitChain)));
-    INF_CHK(inf_ensure(&S.d_res, &S.d_res_cap, nch * sizeof(ChainRes)));
-    if (!S.d_ticket) INF_CHK(hipMalloc(&S.d_ticket, 64));
-    INF_CHK(hipMemcpyAsync(S.d_chains, chains.data(), nch * sizeof(EmitChain), hipMemcpyHostToDevice, s));
-    INF_CHK(hipMemsetAsync(S.d_ticket, 0, 64, s));
-    uint8_t* d_out;
-    const bool direct = (flags & 2u) != 0;
-    if (direct) d_out = out;
-    else {
-        INF_CHK(inf_ensure(&S.d_out, &S.d_out_cap, dict_len + total + 64));
-        d_out = (uint8_t*)S.d_out;
-        if (dict_len) INF_CHK(hipMemcpyAsync(d_out, out, dict_len, hipMemcpyHostToDevice, s));
-    }
-    const uint64_t nbytes = dict_len + total;
-    if ((nbytes + 31) / 32 > 0xFFFFFFFFull) return -2;       // u32 group indices in the resolve lists
-    const uint64_t npw = (nbytes + 31) / 32;
-    INF_CHK(inf_ensure(&S.d_ref, &S.d_ref_cap, nbytes * 4 + 64));
-    INF_CHK(inf_ensure(&S.d_pend, &S.d_pend_cap, npw * 4 + 64));
-    INF_CHK(hipMemsetAsync(S.d_pend, 0, npw * 4 + 64, s));
-    if (!S.h_cnt) INF_CHK(hipHostMalloc(&S.h_cnt, 64, 0));
-    hipEvent_t e2 = S.ev[4], e3 = S.ev[5];
-    INF_CHK(hipEventRecord(e2, s));
-    if (!S.d_ph) INF_CHK(hipMalloc(&S.d_ph, (size_t)std::max(COUNT_WAVES, EMIT_WAVES) * sizeof(wv::PhArr)));
-    static const uint32_t emit_grid = wave_grid(ndfl_inflate_emit_wave_kernel, EMIT_WAVES, "NDFL_EMIT_WPC");
-    hipLaunchKernelGGL(ndfl_inflate_emit_wave_kernel, dim3(std::min<uint32_t>(nch, emit_grid)), dim3(64), 0, s, d_w,
-                       nwords, nbits, (const EmitChain*)S.d_chains, nch, (uint32_t*)S.d_ticket, d_out,
-                       (ChainRes*)S.d_res, (const uint64_t*)S.d_cands, ncand, (uint32_t*)S.d_ref, (uint32_t*)S.d_pend,
-                       pool, (wv::PhArr*)S.d_ph, stats_on ? (uint32_t*)S.d_stats : nullptr, (const uint64_t*)nullptr,
-                       (const uint32_t*)nullptr, (const uint32_t*)nullptr);
-    INF_CHK(hipGetLastError());
-    INF_CHK(hipEventRecord(e3, s));
-    std::vector<ChainRes> er(nch);
-    INF_CHK(hipMemcpyAsync(er.data(), S.d_res, nch * sizeof(ChainRes), hipMemcpyDeviceToHost, s));
-    INF_CHK(hipStreamSynchronize(s));
-    ht[4] = hnow();
-    float ms = 0;
-    hipEventElapsedTime(&ms, e2, e3);
-    S.last_ms_emit = ms;
-    if (stats_on) {
-        uint64_t t64[48];
-        INF_CHK(hipMemcpy(t64, (const uint32_t*)S.d_stats + SW_CLOCK64, sizeof(t64), hipMemcpyDeviceToHost));
-        const double span = (double)(t64[17] - ~t64[18]);
-        fprintf(stderr, "[ndfl] emit waves %llu: busy %.1f ms x waves, span %.3f ms, occupancy %.3f, longest chain %.3f ms\n",
-                (unsigned long long)t64[19], t64[16] * 1e-5, span * 1e-5, t64[19] ? t64[16] / (span * t64[19]) : 0.0,
-                t64[20] * 1e-5);
-    }
-    if (deferred) {
-        S.pending = true;
-        S.p_out = d_out; S.p_nbytes = nbytes; S.p_dict_len = dict_len;
-    } else {
-        uint64_t groups = 0;
-        const int rr = resolve_rounds(S, s, d_out, nbytes, &groups);
-        if (rr) return rr;
-        S.resolved_groups = groups;
-    }
-    INF_CHK(hipEventRecord(e3, s));
-    INF_CHK(hipStreamSynchronize(s));
-    float ms2 = 0;
-    hipEventElapsedTime(&ms2, S.ev[0], e3);
-    S.last_ms_wall = ms2;
-    hipEventElapsedTime(&ms2, e2, e3);
-    *last_ms = ms2;
-    ht[5] = hnow();
-    if (htime) fprintf(stderr, "[ndfl] inflate host ms: finder+starts %.2f count+repairs %.2f link %.2f emit %.2f resolve %.2f\n",
-                       ht[1] - ht[0], ht[2] - ht[1], ht[3] - ht[2], ht[4] - ht[3], ht[5] - ht[4]);
-    // first error in stream order (the emit pass also checks the dictionary bound exactly)
-    for (uint32_t k = 0; k < nch; k++) {
-        if (er[k].status == ST_ERROR) {
-            if (partial && er[k].reason == R_UEOS) {
-                // the input is a prefix of the stream: stop at the last block boundary reached
-                const uint64_t produced = chains[k].out_off - dict_len + er[k].bnd_cnt;
-                if (!direct && produced) INF_CHK(hipMemcpy(out + dict_len, d_out + dict_len, produced, hipMemcpyDeviceToHost));
-                *out_len = produced;
-                *consumed_bits = er[k].bnd_bit;
-                return NEED_INPUT;
-            }
-            const uint64_t produced = chains[k].out_off - dict_len + er[k].out_count;
-            if (!direct && produced) INF_CHK(hipMemcpy(out + dict_len, d_out + dict_len, produced, hipMemcpyDeviceToHost));
-            *out_len = produced;
-            *consumed_bits = er[k].end_bit;
-            return (int)er[k].reason;
-        }
-    }
-    if (!direct && total) INF_CHK(hipMemcpy(out + dict_len, d_out + dict_len, total, hipMemcpyDeviceToHost));
-    *out_len = total;
-    *consumed_bits = stop_bit;
-    return 0;
-}
-
-// First confirmed block boundary at or past from_bit, looking at most window_bits ahead (NONE if
-// none): the finder and count passes of inflate_run on that window, without the emit.
-static int inflate_sync(InflateScratch& S, hipStream_t s, const uint8_t* in, uint64_t in_len, uint64_t from_bit,
-                        uint64_t window_bits, uint32_t flags, uint64_t* sync_bit, double* last_ms) {
-    uint64_t olen = 0, bits = 0;
-    const uint64_t end = std::min(in_len * 8, from_bit + window_bits);
-    if (from_bit >= end) { *sync_bit = inf::NONE; return 0; }
-    return inflate_run(S, s, in, in_len, from_bit, end, nullptr, 0, 0, &olen, &bits, flags, false, last_ms, false,
-                       sync_bit);
-}
-
 // The last n bytes of a deferred-window range decode's output once the caller has written the
 // window, without resolving the rest: each byte follows its back-references (pending bytes only;
 // window bytes are never pending) to a final byte.  A chain longer than TAIL_STEPS sets *fail.
@@ -2254,52 +1151,4 @@ ndfl_inflate_tail_map_kernel(const uint32_t* pend, const uint32_t* ref, const ui
         if (++steps > TAIL_STEPS) { atomicOr(fail, 1u); return; }
     }
     dst[k] = p < dict_len ? (uint32_t)p : TAIL_LITERAL | out[p];
-}
-
-static int inflate_tail_map(InflateScratch& S, hipStream_t s, uint64_t n, uint32_t* dst) {
-    if (!S.pending) return -5;
-    if (n > S.p_nbytes) return -1;
-    if (n == 0) return 0;
-    if (!S.h_cnt) INF_CHK(hipHostMalloc(&S.h_cnt, 64, 0));
-    uint32_t* d_fail = (uint32_t*)S.d_stats + SW_TAIL_FAIL;
-    INF_CHK(hipMemsetAsync(d_fail, 0, 4, s));
-    hipLaunchKernelGGL(ndfl_inflate_tail_map_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s,
-                       (const uint32_t*)S.d_pend, (const uint32_t*)S.d_ref, (const uint8_t*)S.p_out, S.p_nbytes - n, n,
-                       S.p_dict_len, dst, d_fail);
-    INF_CHK(hipGetLastError());
-    uint32_t* h = (uint32_t*)S.h_cnt;
-    INF_CHK(hipMemcpyAsync(h + 8, d_fail, 4, hipMemcpyDeviceToHost, s));
-    INF_CHK(hipStreamSynchronize(s));
-    return h[8] ? -6 : 0;
-}
-
-static int inflate_tail(InflateScratch& S, hipStream_t s, uint64_t n, uint8_t* dst) {
-    if (!S.pending) return -5;
-    if (n > S.p_nbytes) return -1;
-    if (n == 0) return 0;
-    if (!S.h_cnt) INF_CHK(hipHostMalloc(&S.h_cnt, 64, 0));
-    uint32_t* d_fail = (uint32_t*)S.d_stats + SW_TAIL_FAIL;
-    INF_CHK(hipMemsetAsync(d_fail, 0, 4, s));
-    hipLaunchKernelGGL(ndfl_inflate_tail_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s,
-                       (const uint32_t*)S.d_pend, (const uint32_t*)S.d_ref, (const uint8_t*)S.p_out, S.p_nbytes - n, n,
-                       dst, d_fail);
-    INF_CHK(hipGetLastError());
-    uint32_t* h = (uint32_t*)S.h_cnt;
-    INF_CHK(hipMemcpyAsync(h + 8, d_fail, 4, hipMemcpyDeviceToHost, s));
-    INF_CHK(hipStreamSynchronize(s));
-    return h[8] ? -6 : 0;
-}
-
-// Second half of a deferred-window range decode: the caller has written the window
-// (out[0, dict_len)); resolve every deferred copy (those that read the window directly or through
-// other copies included).  *n_resolved = pending 32-byte groups at the start.
-static int inflate_resolve(InflateScratch& S, hipStream_t s, uint64_t* n_resolved) {
-    using namespace inf;
-    *n_resolved = 0;
-    if (!S.pending) return -5;
-    S.pending = false;
-    const int rr = resolve_rounds(S, s, S.p_out, S.p_nbytes, n_resolved);
-    if (rr) return rr;
-    S.resolved_groups = *n_resolved;
-    return 0;
 }

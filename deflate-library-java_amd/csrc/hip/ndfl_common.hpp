@@ -74,6 +74,22 @@ struct Knobs {
     }
 };
 
+// A device buffer that only grows (a context's scratch).  ensure(0) on an empty one leaves p null: ask for a byte at least.
+struct DevBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    hipError_t ensure(size_t n) {
+        if (n <= cap) return hipSuccess;
+        if (p) { hipFree(p); p = nullptr; cap = 0; }
+        size_t want = n < 4096 ? 4096 : n;
+        hipError_t e = hipMalloc(&p, want);
+        if (e == hipSuccess) cap = want;
+        return e;
+    }
+    void release() { if (p) hipFree(p); p = nullptr; cap = 0; }
+    template <class T> T* as() const { return (T*)p; }
+};
+
 #define NDFL_WAVE 64
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));

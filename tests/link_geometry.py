@@ -1,11 +1,11 @@
 """Hand-built streams for the decoder's candidate list and chain linking at their list, tile and range limits.
 
-Between the count pass and the emit pass the decoder (csrc/hip/inflate_kernels.hip, inflate_devlink) turns the
+Between the count pass and the emit pass the decoder (csrc/capi/ndfl_inflate.cpp, Decode::devlink) turns the
 header finder's per-segment lists into one sorted candidate list (ndfl_inflate_segsum / segscan / compact /
 cand_slice), marks stored-header aliases (alias_mark / alias_copy), orders the chains for the count pass
 (order_count / order), links them from the range start by pointer jumping (link_init / jump / path), orders the
 linked chains for the emit pass (emit_order_count / emit_order) and picks the first error (first_error / summary).
-The host linker of inflate_run (NDFL_HOST_LINK=1) is a second implementation of the same stage.  Every one of
+The host linker, Decode::hostlink (NDFL_HOST_LINK=1), is a second implementation of the same stage.  Every one of
 these has a limit at an exact count or bit position: tiles of SCAN_TILE = 2,048 items, 256-thread grid-stride
 loops, ceil(log2 n) jump levels, 24 buckets of 32 Kibit, the 10-bit alias window, two binary searches on the range,
 an atomicMin.  No stream written by an encoder chooses its chain structure; these do:

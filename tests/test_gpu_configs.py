@@ -5,7 +5,8 @@
   * config 5: the random+repeat corpus (corpus.c5_random_repeat, seed 0xC5): a 256 MiB RLE_DYNAMIC
     GPU encode equal to the oracle's bytes, and the GPU round trip;
   * streams with more dynamic headers per 64 KiB finder segment than the finder keeps (SEG_CAP = 256,
-    inflate_kernels.hip): chunk_len = 64 RLE_DYNAMIC, decoded equal to the oracle;
+    csrc/hip/inflate_kernels.hip; the host side: csrc/capi/ndfl_inflate.cpp): chunk_len = 64 RLE_DYNAMIC,
+    decoded equal to the oracle;
   * the one-kernel encoder (NDFL_DEFLATE_FUSED=1) against the oracle.
 """
 import io

@@ -1,8 +1,8 @@
 """GPU decode of the candidate-list and chain-linking limit cases of tests/link_geometry.py (what each case reaches is
 pinned on the CPU by tests/test_link_geometry_cpu.py), through four contexts:
 
-    default      the device-side list and linking (inflate_devlink)
-    host_link    NDFL_HOST_LINK=1: the host linker of inflate_run, the second implementation of the stage
+    default      the device-side list and linking (Decode::devlink)
+    host_link    NDFL_HOST_LINK=1: the host linker (Decode::hostlink), the second implementation of the stage
     no_alias     NDFL_NO_ALIAS=1: every stored-header alias counted as a chain of its own
     w4           NDFL_COUNT_W=4: the workgroup count kernel, its own chain loop
 
