@@ -347,6 +347,9 @@ __device__ __forceinline__ bool strict_stored(const In& in, uint64_t p) {
 // input; dynamic headers need a complete code-length code (Kraft sum exactly 1 over the HCLEN+4
 // 3-bit lengths); stored headers need LEN == ~NLEN at the next byte boundary and zero padding.
 // Survivors (about 1 in 1000 positions) go to a global list for the strict stage.
+// (amdgpu_waves_per_eu(N) is the least occupancy the register allocator must leave room for, not the
+// occupancy: the finder's 40 VGPRs and 17.5 KB of LDS give 8 waves per SIMD, which
+// tests/test_finder_resources.py pins)
 #ifndef NDFL_FIND_WPE
 #define NDFL_FIND_WPE 3
 #endif
@@ -361,7 +364,10 @@ namespace inf {
 // summed by five lookups of a 4,096-entry table of the Kraft sums of four lengths (kr4).  About 30
 // operations per such position (round 4; a bit-sliced Kraft test at every position took 451 per
 // 32 positions).  A pass takes at most FIND_TAKE positions per lane (a dense pattern takes more
-// passes).
+// passes; on the config-4 mix some lane of a wave has more than 8 in 1.5 % of the words).
+// A wave whose 64 words and the three after them lie inside the input and the scan range (all but
+// the input's last waves) loads them unchecked and needs no `valid` mask; the bounds tests of a
+// tested position are done in the other waves only.
 constexpr uint32_t FIND_TAKE = 8;
 constexpr uint32_t FIND_CLIST = 64 * FIND_TAKE;
 constexpr uint32_t FIND_CCAP = 1024;               // survivors listed in LDS per workgroup (131,072 positions; ~65 on average)
@@ -377,45 +383,62 @@ __device__ __forceinline__ void find_spill(uint64_t v, uint64_t* qlist, uint32_t
     const uint32_t g = atomicAdd(qcount, 1u);
     if (g < qcap) qlist[g] = v;
 }
-__device__ __forceinline__ void find_word_wave(const In& in, uint64_t t, uint64_t scan_end, uint32_t* cand,
-                                               uint32_t* ncand, FindWaveScratch& fw, const uint16_t* kr4, uint64_t pb,
-                                               uint64_t* qlist, uint32_t* qcount, uint32_t qcap) {
+// tw0: the wave's first word (wave-uniform); rel0: its first bit as an offset from `pb`.
+__device__ __forceinline__ void find_word_wave(const In& in, uint64_t tw0, uint32_t rel0, uint64_t scan_end,
+                                               uint32_t* cand, uint32_t* ncand, FindWaveScratch& fw, const uint16_t* kr4,
+                                               uint64_t pb, uint64_t* qlist, uint32_t* qcount, uint32_t qcap) {
     const uint64_t nbits = in.nbits;
-    const int lane = threadIdx.x & 63;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t t = tw0 + lane;
     const uint64_t p0 = t * 32;
-    const uint32_t w0 = in.ld(t), w1 = in.ld(t + 1), w2 = in.ld(t + 2), w3 = in.ld(t + 3);
+    // an inner wave: every position of its 64 words is valid and in range, and every word that a lane
+    // reads exists (nbits <= 32 nwords, scan_end <= nbits)
+    const bool inner = (tw0 + 67) * 32 <= nbits && (tw0 + 64) * 32 <= scan_end;
+    uint32_t w0, w1, w2, w3, valid = 0xFFFFFFFFu;
+    if (inner) {
+        const uint32_t* q = in.w + tw0 + lane;
+        w0 = q[0]; w1 = q[1]; w2 = q[2]; w3 = q[3];
+    } else {
+        w0 = in.ld(t); w1 = in.ld(t + 1); w2 = in.ld(t + 2); w3 = in.ld(t + 3);
+        if (p0 + 35 > nbits) valid = (nbits >= p0 + 3) ? (uint32_t)((1ull << (nbits - p0 - 2)) - 1) : 0u;
+        if (p0 + 32 > scan_end) valid &= p0 < scan_end ? (uint32_t)((1ull << (scan_end - p0)) - 1) : 0u;
+    }
     const uint64_t W = (uint64_t)w0 | ((uint64_t)w1 << 32);
     const uint32_t b1 = (uint32_t)(W >> 1), b2 = (uint32_t)(W >> 2);
-    uint32_t valid = 0xFFFFFFFFu;
-    if (p0 + 35 > nbits) valid = (nbits >= p0 + 3) ? (uint32_t)((1ull << (nbits - p0 - 2)) - 1) : 0u;
-    if (p0 + 32 > scan_end) valid &= p0 < scan_end ? (uint32_t)((1ull << (scan_end - p0)) - 1) : 0u;
     const uint32_t notfinal = ~w0;
     const uint32_t h4 = (uint32_t)(W >> 4), h5 = (uint32_t)(W >> 5), h6 = (uint32_t)(W >> 6),
                    h7 = (uint32_t)(W >> 7), d9 = (uint32_t)(W >> 9), d10 = (uint32_t)(W >> 10),
                    d11 = (uint32_t)(W >> 11), d12 = (uint32_t)(W >> 12);
     const uint32_t big = (h4 & h5 & h6 & h7) | (d9 & d10 & d11 & d12);     // HLIT or HDIST >= 30
     const uint32_t pm = ~b1 & b2 & valid & notfinal & ~big;         // before the Kraft test
-    // stored headers: LEN == ~NLEN (as find_word)
-    const uint64_t W12 = (uint64_t)w1 | ((uint64_t)w2 << 32);
-    const uint32_t x1 = (uint32_t)(W >> 8), x2 = (uint32_t)(W >> 16), x3 = (uint32_t)(W >> 24), x4 = w1,
-                   x5 = (uint32_t)(W12 >> 8);
-#define NDFL_LENOK(x) ((((x) ^ ((x) >> 16)) & 0xFFFFu) == 0xFFFFu)
-    const uint32_t okm = (NDFL_LENOK(x1) ? 0x0000003Fu : 0u) | (NDFL_LENOK(x2) ? 0x00003FC0u : 0u) |
-                         (NDFL_LENOK(x3) ? 0x003FC000u : 0u) | (NDFL_LENOK(x4) ? 0x3FC00000u : 0u) |
-                         (NDFL_LENOK(x5) ? 0xC0000000u : 0u);
-#undef NDFL_LENOK
-    uint32_t m0 = ~b1 & ~b2 & valid & notfinal & okm;
-    while (m0) {
-        const uint32_t o = __builtin_ctz(m0);
-        m0 &= m0 - 1;
-        const uint32_t q = o + 3, al = (q + 7) & ~7u;
-        const uint32_t pad = al > q ? (uint32_t)(W >> q) & ((1u << (al - q)) - 1u) : 0u;
-        if (pad) continue;
-        const uint32_t ln = (al < 32 ? (uint32_t)(W >> al) : (uint32_t)(W12 >> (al - 32))) & 0xFFFFu;
-        if (p0 + al + 32 + 8ull * ln <= nbits) {
-            uint32_t k = atomicAdd(ncand, 1u);
-            if (k < FIND_CCAP) cand[k] = (uint32_t)(p0 + o - pb);
-            else find_spill(p0 + o, qlist, qcount, qcap);
+    // stored headers: LEN == ~NLEN at one of the five byte offsets 1..5 that the word's positions
+    // align to.  With V the window w0..w2 and n = ~(V ^ (V >> 16)), LEN == ~NLEN at byte k is "bytes k
+    // and k + 1 of n are zero", i.e. byte k of m = n | (n >> 8) is zero: one xor per word and a
+    // zero-byte test say whether any offset matches.  Hardly a word has one, so the per-offset masks
+    // and the position loop are built only in a wave in which some lane has.
+    const uint32_t nlo = ~(w0 ^ (uint32_t)(W >> 16));
+    const uint32_t nhi = ~(w1 ^ ((w1 >> 16) | (w2 << 16)));
+    const uint32_t mlo = nlo | ((nlo >> 8) | (nhi << 24)), mhi = nhi | (nhi >> 8);
+    const uint32_t m14 = (mlo >> 8) | (mhi << 24);                  // bytes 1..4 of m
+    const bool lenok = (((m14 - 0x01010101u) & ~m14 & 0x80808080u) | (uint32_t)((mhi & 0xFF00u) == 0)) != 0;
+    if (__any(lenok)) {
+        const uint64_t W12 = (uint64_t)w1 | ((uint64_t)w2 << 32);
+        const uint32_t okm = ((m14 & 0x000000FFu) ? 0u : 0x0000003Fu) | ((m14 & 0x0000FF00u) ? 0u : 0x00003FC0u) |
+                             ((m14 & 0x00FF0000u) ? 0u : 0x003FC000u) | ((m14 & 0xFF000000u) ? 0u : 0x3FC00000u) |
+                             ((mhi & 0x0000FF00u) ? 0u : 0xC0000000u);
+        uint32_t m0 = ~b1 & ~b2 & valid & notfinal & okm;
+        while (m0) {
+            const uint32_t o = __builtin_ctz(m0);
+            m0 &= m0 - 1;
+            const uint32_t q = o + 3, al = (q + 7) & ~7u;
+            const uint32_t pad = al > q ? (uint32_t)(W >> q) & ((1u << (al - q)) - 1u) : 0u;
+            if (pad) continue;
+            const uint32_t ln = (al < 32 ? (uint32_t)(W >> al) : (uint32_t)(W12 >> (al - 32))) & 0xFFFFu;
+            if (p0 + al + 32 + 8ull * ln <= nbits) {
+                uint32_t k = atomicAdd(ncand, 1u);
+                if (k < FIND_CCAP) cand[k] = rel0 + (lane << 5) + o;
+                else find_spill(p0 + o, qlist, qcount, qcap);
+            }
         }
     }
     // dynamic headers
@@ -424,7 +447,6 @@ __device__ __forceinline__ void find_word_wave(const In& in, uint64_t t, uint64_
         const uint32_t e1 = __shfl(w1, 63, 64), e2 = __shfl(w2, 63, 64), e3 = __shfl(w3, 63, 64);
         if (lane < 3) fw.w[64 + lane] = lane == 0 ? e1 : lane == 1 ? e2 : e3;
     }
-    const uint64_t tw0 = t - (uint64_t)lane;                        // the wave's first word
     uint32_t rem = pm;
     while (__any(rem != 0)) {                                        // (uniform; no empty scan pass)
         const uint32_t cnt = min((uint32_t)__popc(rem), FIND_TAKE);
@@ -458,11 +480,12 @@ __device__ __forceinline__ void find_word_wave(const In& in, uint64_t t, uint64_
             F &= (1ull << (3 * ncl)) - 1;                            // the HCLEN + 4 lengths (<= 57 bits)
             const uint32_t ks = (uint32_t)kr4[F & 4095] + kr4[(F >> 12) & 4095] + kr4[(F >> 24) & 4095] +
                                 kr4[(F >> 36) & 4095] + kr4[(F >> 48) & 4095];
-            const uint64_t p = (tw0 + lw) * 32 + o;
-            if (ks == 128 && p + 17 + 3 * ncl <= nbits) {
+            bool ok = ks == 128;
+            if (!inner) ok = ok && tw0 * 32 + c + 17 + 3 * ncl <= nbits;   // (c = 32 lw + o; an inner wave's fields end inside the input)
+            if (ok) {
                 uint32_t k = atomicAdd(ncand, 1u);
-                if (k < FIND_CCAP) cand[k] = (uint32_t)(p - pb) | (1u << 31);
-                else find_spill(p | (1ull << 63), qlist, qcount, qcap);
+                if (k < FIND_CCAP) cand[k] = (rel0 + c) | (1u << 31);
+                else find_spill((pb + rel0 + c) | (1ull << 63), qlist, qcount, qcap);
             }
         }
         __builtin_amdgcn_wave_barrier();                             // (the list is rewritten next)
@@ -470,14 +493,24 @@ __device__ __forceinline__ void find_word_wave(const In& in, uint64_t t, uint64_
 }
 // Kraft sums of four 3-bit lengths (index: four fields, the first in the low bits), x 1/128.  (Ten
 // lookups of a 64-entry two-length table -- one entry per LDS bank, no bank conflicts -- measured
-// slower: finder phase 6.12 -> 6.50 ms, round 5.)
-__device__ __forceinline__ void kr4_fill(uint16_t* kr4) {
-    for (uint32_t i = threadIdx.x; i < 4096; i += blockDim.x) {
+// slower: finder phase 6.12 -> 6.50 ms, round 5.)  The table is a constant of the code object; a
+// workgroup copies it to LDS with 16-byte loads (computing it per workgroup took ~320 vector
+// instructions per thread, for 16 words per thread).
+struct Kr4Table { uint16_t v[4096]; };
+constexpr Kr4Table kr4_make() {
+    Kr4Table t{};
+    for (uint32_t i = 0; i < 4096; i++) {
         uint32_t s = 0;
-#pragma unroll
         for (int f = 0; f < 4; f++) { const uint32_t l = (i >> (3 * f)) & 7u; s += l ? 128u >> l : 0u; }
-        kr4[i] = (uint16_t)s;
+        t.v[i] = (uint16_t)s;
     }
+    return t;
+}
+__device__ const Kr4Table KR4_TABLE __attribute__((aligned(16))) = kr4_make();
+__device__ __forceinline__ void kr4_copy(uint16_t* kr4) {
+    const u32x4* src = (const u32x4*)KR4_TABLE.v;
+    u32x4* dst = (u32x4*)kr4;
+    for (uint32_t i = threadIdx.x; i < sizeof(Kr4Table) / 16; i += blockDim.x) dst[i] = src[i];
 }
 
 }  // namespace inf
@@ -489,16 +522,18 @@ ndfl_inflate_find_compact_kernel(const uint32_t* w, uint64_t nwords, uint64_t nb
     using namespace inf;
     __shared__ uint32_t cand[FIND_CCAP];
     __shared__ uint32_t ncand, gbase;
-    __shared__ uint16_t kr4[4096];
+    __shared__ __attribute__((aligned(16))) uint16_t kr4[4096];
     __shared__ FindWaveScratch fws[4];
-    kr4_fill(kr4);
+    kr4_copy(kr4);
     if (threadIdx.x == 0) ncand = 0;
     __syncthreads();
     In in{w, nwords, nbits};
-    const uint64_t pb = (w_lo + (uint64_t)blockIdx.x * FIND_WPT * 256) * 32;    // the workgroup's first bit
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint64_t wg0 = w_lo + (uint64_t)blockIdx.x * FIND_WPT * 256;          // the workgroup's first word
+    const uint64_t pb = wg0 * 32;                                               // and its first bit
     for (uint32_t kk = 0; kk < FIND_WPT; kk++) {
-        const uint64_t tt = ((uint64_t)blockIdx.x * FIND_WPT + kk) * blockDim.x + threadIdx.x;
-        find_word_wave(in, w_lo + tt, scan_end, cand, &ncand, fws[threadIdx.x >> 6], kr4, pb, qlist, qcount, qcap);
+        const uint32_t wo = kk * 256 + wave * 64;                               // the wave's first word of this round
+        find_word_wave(in, wg0 + wo, wo * 32, scan_end, cand, &ncand, fws[wave], kr4, pb, qlist, qcount, qcap);
     }
     // the workgroup's LDS survivors -> the global survivor list (one global atomic)
     __syncthreads();
